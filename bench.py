@@ -2,16 +2,21 @@
 K(X,X*), N^2 C variance contraction, mean) + Monte-Carlo uEI + top-16 selection [+ ONE all-reduce over ranks].
 Default workload = BASELINE.json configs[2]: m=4 RBF-ARD, N=4096, d=8, S=1024 MC samples, C=65536 candidates, fp64.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 
-Prints ONE JSON line on rank 0:
+A plain run sets up (one GP fit, inputs resident), runs W warm-up steps, times K steps and prints ONE JSON line on rank 0:
   value / ms_per_step         K steps with the inputs (X*, W) resident in HBM, total wall time between two fences, max over ranks
   ms_per_step_median          median of the K per-step times of that region
+--dump-outputs DIR writes what the last timed step returned (the top-16 candidate indices and their acquisition values) as
+DIR/top16_index.npy and DIR/top16_value.npy, float64; the inputs come from --seed, so two builds can be compared output for output.
+--full adds the measurements below (HIP events around the kernels during the K timed steps, extra fits and steps, the CPU run):
+  gp_fit_ms                   median of seven full fits after four warm-up fits
   transfers_included          the SAME K steps once more with the H2D of X* and the D2H of the scores inside every step
                               (SURVEY 8d Metric 1 as worded: "host<->device transfer of X* and acq included; median")
   roofline                    dominant kernel (variance GEMM): algorithmic flop / HIP-event time, in-run
   roofline_fit                K(X,X) build GB/s vs HBM peak and Cholesky + inverse TFLOP/s vs fp64-MFMA peak, HIP events in-run
+  int8_variance_contraction   the same K steps once more with option predict_i8 (fp64 runs at one rank)
   cpu_baseline                the oracle (NumPy/SciPy port) on a bounded sample of the same workload, plus the reference's own
                               loop structure (uEI_noiseless.py:63-83) timed on a small sample and its survey-time figure
 """
@@ -77,7 +82,11 @@ def parse():
     ap.add_argument("--config", type=int, default=3, choices=[2, 3, 5],
                     help="BASELINE.json config preset (1-based as in SURVEY 8d): 2 = N1024 d6 S256 C8192; 3 = headline; "
                          "5 = m8 Matern52 N8192 d12 S4096 noise 1e-4 (add --f32 for the fp32 contraction it names)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the fit, the transfers, the int8 contraction, the roofline figures and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's top-16 indices and acquisition values to DIR/*.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-sample", type=int, default=2048, help="candidates in the CPU-baseline sample")
     ap.add_argument("--f32", action="store_true", help="fp32 variance contraction (option predict_f32; BASELINE configs[4] arithmetic)")
     ap.add_argument("--i8", action="store_true", help="variance contraction in exact int8 digit products (option predict_i8: six radix-254 digits per operand column, fp64 recombination)")
@@ -87,7 +96,10 @@ def parse():
                          "all-reduce over a device-packed buffer (torch), or native with torch as the fallback (auto)")
     ap.add_argument("--shard-fit", action="store_true", help="N>1: every rank factorizes only its contiguous share of the outputs, inverse factors broadcast over RCCL (option shard_fit)")
     ap.add_argument("--check", action="store_true", help="parity-check a slice against the oracle before timing")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 PRESETS = {2: dict(N=1024, d=6, m=4, S=256, C=8192, kernel="rbf", seed=1236),
@@ -174,46 +186,50 @@ def main():
 
     # ---- GP fit (metric 2): K build + Cholesky + inverse factor + alpha for all m outputs, incl. H2D
     model.incremental = False                    # time the FULL fit (an unchanged X would otherwise only refresh alpha)
-    for _ in range(4):                           # warm-up: allocations, stream creation, and the clock ramp of a process that has just started
-        model.updateModel(p["X"], p["Y"])        # (successive fits of a fresh process read 7.05, 6.67, 6.59, 6.50, 6.52 ms)
-    fit_ms = []
-    for _ in range(7):                           # (median of seven, as the phase timers below)
-        t0 = time.perf_counter()
+    fit_ms, roofline_fit = None, None
+    if not a.full:
+        model.updateModel(p["X"], p["Y"])        # set-up only: the plain run times the acquisition steps
+    else:
+        for _ in range(4):                           # warm-up: allocations, stream creation, and the clock ramp of a process that has just started
+            model.updateModel(p["X"], p["Y"])        # (successive fits of a fresh process read 7.05, 6.67, 6.59, 6.50, 6.52 ms)
+        fit_ms = []
+        for _ in range(7):                           # (median of seven, as the phase timers below)
+            t0 = time.perf_counter()
+            model.updateModel(p["X"], p["Y"])
+            fit_ms.append((time.perf_counter() - t0) * 1e3)
+        fit_ms = float(np.median(fit_ms))
+        model.set_option("profile", 1)               # more fits with HIP events around the phases: one untimed (it creates the events), then three
         model.updateModel(p["X"], p["Y"])
-        fit_ms.append((time.perf_counter() - t0) * 1e3)
-    fit_ms = float(np.median(fit_ms))
-    model.set_option("profile", 1)               # more fits with HIP events around the phases: one untimed (it creates the events), then three
-    model.updateModel(p["X"], p["Y"])
-    for name in ("kbuild", "cholesky", "inverse", "alpha"):
-        phase(name)
-    # seven fits read one by one, the MEDIAN reported: about one fit in twelve of a long-running process is 0.5-0.8 ms slower (the host stalls
-    # once in the middle of enqueuing it and the GPU runs dry: seen as 4.57 / 4.57 / 4.86 / 4.58 ms for successive groups of three)
-    nfit = 7
-    per_fit = []
-    for _ in range(nfit):
-        model.updateModel(p["X"], p["Y"])
-        per_fit.append({name: phase(name) for name in ("kbuild", "cholesky", "inverse", "alpha")})
-    model.set_option("profile", 0)
-    ph = {name: (float(np.median([f[name][0] for f in per_fit])) * nfit, sum(f[name][1] for f in per_fit)) for name in ("kbuild", "cholesky", "inverse", "alpha")}
-    ci_per_fit = [f["cholesky"][0] + f["inverse"][0] for f in per_fit]
-    Np = (a.N + 127) // 128 * 128
-    kb_ms = float(np.median([f["kbuild"][0] / max(1, f["kbuild"][1]) for f in per_fit]))
-    ci_ms = float(np.median(ci_per_fit))
-    m_local = a.m if not a.shard_fit else len(range(rank, a.m, world))
-    kb_bytes = kbuild_bytes(Np, m_local)
-    ci_flops = 2.0 * m_local * float(a.N) ** 3 / 3.0          # N^3/3 (Cholesky) + N^3/3 (triangular inverse) per output
-    roofline_fit = {
-        "kbuild": {"kernel": "build_train_kernel (K(X,X), tiles on/above the diagonal)", "bound": "hbm", "bytes_per_launch": kb_bytes,
-                   "launch_ms": kb_ms, "achieved": kb_bytes / (kb_ms * 1e-3) / 1e9 if kb_ms > 0 else 0.0, "peak": HBM_PEAK_GBS,
-                   "unit": "GB/s", "frac": (kb_bytes / (kb_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if kb_ms > 0 else 0.0,
-                   "jitter_attempts_per_fit": ph["kbuild"][1] / nfit},
-        "cholesky_inverse": {"kernels": "blocked Cholesky (diagonal-block kernel + fp64-MFMA panel solves / trailing updates) + triangular inverse",
-                             "bound": "mfma", "algorithmic_flops": ci_flops, "ms": ci_ms, "ms_per_fit": ci_per_fit, "ms_definition": "median of %d fits" % nfit,
-                             "cholesky_ms": ph["cholesky"][0] / nfit,
-                             "inverse_ms": ph["inverse"][0] / nfit, "alpha_lml_trainmean_ms": ph["alpha"][0] / nfit,
-                             "achieved": ci_flops / (ci_ms * 1e-3) / 1e12 if ci_ms > 0 else 0.0, "peak": FP64_MFMA_PEAK_TFLOPS,
-                             "unit": "TFLOP/s", "frac": (ci_flops / (ci_ms * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS) if ci_ms > 0 else 0.0},
-    }
+        for name in ("kbuild", "cholesky", "inverse", "alpha"):
+            phase(name)
+        # seven fits read one by one, the MEDIAN reported: about one fit in twelve of a long-running process is 0.5-0.8 ms slower (the host stalls
+        # once in the middle of enqueuing it and the GPU runs dry: seen as 4.57 / 4.57 / 4.86 / 4.58 ms for successive groups of three)
+        nfit = 7
+        per_fit = []
+        for _ in range(nfit):
+            model.updateModel(p["X"], p["Y"])
+            per_fit.append({name: phase(name) for name in ("kbuild", "cholesky", "inverse", "alpha")})
+        model.set_option("profile", 0)
+        ph = {name: (float(np.median([f[name][0] for f in per_fit])) * nfit, sum(f[name][1] for f in per_fit)) for name in ("kbuild", "cholesky", "inverse", "alpha")}
+        ci_per_fit = [f["cholesky"][0] + f["inverse"][0] for f in per_fit]
+        Np = (a.N + 127) // 128 * 128
+        kb_ms = float(np.median([f["kbuild"][0] / max(1, f["kbuild"][1]) for f in per_fit]))
+        ci_ms = float(np.median(ci_per_fit))
+        m_local = a.m if not a.shard_fit else len(range(rank, a.m, world))
+        kb_bytes = kbuild_bytes(Np, m_local)
+        ci_flops = 2.0 * m_local * float(a.N) ** 3 / 3.0          # N^3/3 (Cholesky) + N^3/3 (triangular inverse) per output
+        roofline_fit = {
+            "kbuild": {"kernel": "build_train_kernel (K(X,X), tiles on/above the diagonal)", "bound": "hbm", "bytes_per_launch": kb_bytes,
+                       "launch_ms": kb_ms, "achieved": kb_bytes / (kb_ms * 1e-3) / 1e9 if kb_ms > 0 else 0.0, "peak": HBM_PEAK_GBS,
+                       "unit": "GB/s", "frac": (kb_bytes / (kb_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if kb_ms > 0 else 0.0,
+                       "jitter_attempts_per_fit": ph["kbuild"][1] / nfit},
+            "cholesky_inverse": {"kernels": "blocked Cholesky (diagonal-block kernel + fp64-MFMA panel solves / trailing updates) + triangular inverse",
+                                 "bound": "mfma", "algorithmic_flops": ci_flops, "ms": ci_ms, "ms_per_fit": ci_per_fit, "ms_definition": "median of %d fits" % nfit,
+                                 "cholesky_ms": ph["cholesky"][0] / nfit,
+                                 "inverse_ms": ph["inverse"][0] / nfit, "alpha_lml_trainmean_ms": ph["alpha"][0] / nfit,
+                                 "achieved": ci_flops / (ci_ms * 1e-3) / 1e12 if ci_ms > 0 else 0.0, "peak": FP64_MFMA_PEAK_TFLOPS,
+                                 "unit": "TFLOP/s", "frac": (ci_flops / (ci_ms * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS) if ci_ms > 0 else 0.0},
+        }
 
     theta = np.array([[0.2 * (j + 1) for j in range(a.m)]])
     U = B.Utility(parameter_dist=B.ParameterDistribution(support=theta, prob_dist=np.ones(1)), device="neg_sq_dist")
@@ -280,21 +296,28 @@ def main():
 
     for _ in range(a.warmup):
         step()
-    model.set_option("profile", 1)
-    lib.bocf_profile_read(handle, None, None, None, 1)
-    for name in ("cross", "acq", "topk", "allreduce"):
-        phase(name)
+    if a.full:                                       # HIP events around the kernels of the timed steps (roofline, per-phase times)
+        model.set_option("profile", 1)
+        lib.bocf_profile_read(handle, None, None, None, 1)
+        for name in ("cross", "acq", "topk", "allreduce"):
+            phase(name)
     dt, per, (top_idx, top_val), ranks = timed(step)
-    ms, launches, flops = ctypes.c_double(), ctypes.c_longlong(), ctypes.c_double()
-    lib.bocf_profile_read(handle, ctypes.byref(ms), ctypes.byref(launches), ctypes.byref(flops), 1)
-    ph2 = {name: phase(name) for name in ("cross", "acq", "topk", "allreduce")}
-    model.set_option("profile", 0)
-    step_with_transfers()
-    dt2, per2, _, _ = timed(step_with_transfers)
+    if a.dump_outputs and rank == 0:                 # what a caller of the timed step receives from its last call
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "top16_index.npy"), np.asarray(top_idx, dtype=np.float64))
+        np.save(os.path.join(a.dump_outputs, "top16_value.npy"), np.asarray(top_val, dtype=np.float64))
+    ph2 = None
+    if a.full:
+        ms, launches, flops = ctypes.c_double(), ctypes.c_longlong(), ctypes.c_double()
+        lib.bocf_profile_read(handle, ctypes.byref(ms), ctypes.byref(launches), ctypes.byref(flops), 1)
+        ph2 = {name: phase(name) for name in ("cross", "acq", "topk", "allreduce")}
+        model.set_option("profile", 0)
+        step_with_transfers()
+        dt2, per2, _, _ = timed(step_with_transfers)
     # the same steps once more with the variance contraction in exact int8 digit products (option predict_i8): reported NEXT TO the fp64 line,
     # never as `value`
     i8_block = None
-    if not a.f32 and not a.i8 and dist is None:
+    if a.full and not a.f32 and not a.i8 and dist is None:
         model.set_option("predict_i8", 1)
         step()
         dt3, per3, (top_idx8, top_val8), _ = timed(step)
@@ -308,25 +331,6 @@ def main():
 
     if rank == 0:
         evals = float(a.C) * a.S * a.steps
-        gemm_ms = ms.value / max(1, launches.value)
-        gemm_flops = flops.value / max(1, launches.value)          # algorithmic: m N^2 C_local per launch
-        ach = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-        peak = FP32_MFMA_PEAK_TFLOPS if a.f32 else FP64_MFMA_PEAK_TFLOPS
-        if a.i8:                                       # priced in int8 operations: 21 digit products per fp64 multiply-add pair
-            gemm_flops *= 21.0
-            ach = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-            peak = INT8_MFMA_PEAK_TOPS
-        traffic, traffic_src, traffic_kernel, traffic_head, traffic_sha = pmc_traffic(a.N, a.m, hi - lo, a.f32)
-        # the 256-row three-buffer kernels take batches from 2048 candidates per pass when the padded N is a multiple of 256 (capi.hip, gemm_f32.hip)
-        big_tiles = (hi - lo) >= 2048 and ((a.N + 127) // 128 * 128) % 256 == 0 and not any(o.startswith("swizzle=") for o in a.option)
-        kernel_name = (("gemm_tn_f32_sumsq256x3_kernel" if big_tiles else "gemm_tn_f32_sumsq_kernel") if a.f32
-                       else ("gemm_tn_f64_sumsq256x3_kernel" if big_tiles else "gemm_tn_f64_kernel<1>"))
-        if a.i8:
-            kernel_name = "slice_operand_kernel<6> + var_i8_kernel<6>"
-            traffic_src = None
-        # a committed counter file is only valid for the kernel SOURCE it was taken on: tools/summarize_profiles.py stamps the git blob hash
-        # of gemm_f64.hip / gemm_f32.hip; a file without the stamp, or with another hash, is stale (traffic = null)
-        traffic_stale = bool(traffic_src and ((traffic_kernel and kernel_name not in traffic_kernel) or traffic_sha != kernel_source_sha(a.f32)))
         rccl_ranks = model._context().stat("comm_world")
         out = {
             "metric": "acquisition evals/sec (candidates x MC-samples/sec), uEI_noiseless batch call; GP-fit ms alongside",
@@ -341,31 +345,51 @@ def main():
                                       % (world, "output-sharded + broadcast" if a.shard_fit else "replicated", carrier),
                        "rccl_ranks_seen": int(rccl_ranks) if carrier == "native" else (int(dist.get_world_size()) if dist is not None else 0)},
             "value_definition": "K steps with X* and W resident in HBM (the driver's contract: value never includes PCIe); SURVEY 8(d) Metric 1 as "
-                                "worded (H2D of X*, D2H of the scores inside every step, median) is the transfers_included block",
-            "transfers_included": {"what": "every step also uploads this rank's X* slice (H2D %d B) and downloads its scores (D2H %d B)"
-                                           % (Xloc.nbytes, 8 * (hi - lo)),
-                                   "value": evals / dt2, "ms_per_step": dt2 / a.steps * 1e3, "ms_per_step_median": float(np.median(per2)) * 1e3},
+                                "worded (H2D of X*, D2H of the scores inside every step, median) is the transfers_included block of --full",
             "per_rank": None if ranks is None else {
                 "ms_per_step": [r[0] / a.steps * 1e3 for r in ranks], "ms_per_step_median": [r[1] * 1e3 for r in ranks],
                 "ms_per_step_min_over_ranks": min(r[0] for r in ranks) / a.steps * 1e3, "ms_per_step_max_over_ranks": max(r[0] for r in ranks) / a.steps * 1e3,
                 "slowest_single_step_ms": max(r[3] for r in ranks) * 1e3,
-                "collective_ms_per_step_rank0": ph2["allreduce"][0] / a.steps,
-                "note": "collective = HIP events around ncclAllReduce(MAX) of 2*world*16+1 doubles on rank 0's stream (it includes the wait for the slowest rank); native carrier only"},
-            "gp_fit_ms": fit_ms,
+                "collective_ms_per_step_rank0": ph2["allreduce"][0] / a.steps if ph2 is not None else None,
+                "note": "collective = HIP events around ncclAllReduce(MAX) of 2*world*16+1 doubles on rank 0's stream (it includes the wait for the slowest rank); native carrier, --full only"},
             "argmax": int(top_idx[0]),
-            "roofline": {"kernel": kernel_name + " (variance contraction V = L^-1 K*, fused column sum-of-squares)",
-                         "bound": "mfma", "achieved": ach, "peak": peak, "unit": "TOP/s (int8)" if a.i8 else "TFLOP/s", "frac": ach / peak,
-                         "traffic": traffic if not traffic_stale else None,
-                         "traffic_source": ("%s (rocprofv3 --pmc passes of this command, kernel %s, taken at git %s)" % (traffic_src, traffic_kernel, traffic_head)
-                                            if traffic_src else None),
-                         "traffic_stale": traffic_stale,
-                         "launch_ms": gemm_ms, "algorithmic_flops_per_launch": gemm_flops,
-                         "other_kernels_ms_per_step": {k: v[0] / a.steps for k, v in ph2.items()}},
-            "roofline_fit": roofline_fit,
         }
+        if a.full:
+            gemm_ms = ms.value / max(1, launches.value)
+            gemm_flops = flops.value / max(1, launches.value)          # algorithmic: m N^2 C_local per launch
+            ach = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+            peak = FP32_MFMA_PEAK_TFLOPS if a.f32 else FP64_MFMA_PEAK_TFLOPS
+            if a.i8:                                       # priced in int8 operations: 21 digit products per fp64 multiply-add pair
+                gemm_flops *= 21.0
+                ach = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+                peak = INT8_MFMA_PEAK_TOPS
+            traffic, traffic_src, traffic_kernel, traffic_head, traffic_sha = pmc_traffic(a.N, a.m, hi - lo, a.f32)
+            # the 256-row three-buffer kernels take batches from 2048 candidates per pass when the padded N is a multiple of 256 (capi.hip, gemm_f32.hip)
+            big_tiles = (hi - lo) >= 2048 and ((a.N + 127) // 128 * 128) % 256 == 0 and not any(o.startswith("swizzle=") for o in a.option)
+            kernel_name = (("gemm_tn_f32_sumsq256x3_kernel" if big_tiles else "gemm_tn_f32_sumsq_kernel") if a.f32
+                           else ("gemm_tn_f64_sumsq256x3_kernel" if big_tiles else "gemm_tn_f64_kernel<1>"))
+            if a.i8:
+                kernel_name = "slice_operand_kernel<6> + var_i8_kernel<6>"
+                traffic_src = None
+            # a committed counter file is only valid for the kernel SOURCE it was taken on: tools/summarize_profiles.py stamps the git blob hash
+            # of gemm_f64.hip / gemm_f32.hip; a file without the stamp, or with another hash, is stale (traffic = null)
+            traffic_stale = bool(traffic_src and ((traffic_kernel and kernel_name not in traffic_kernel) or traffic_sha != kernel_source_sha(a.f32)))
+            out["transfers_included"] = {"what": "every step also uploads this rank's X* slice (H2D %d B) and downloads its scores (D2H %d B)"
+                                                 % (Xloc.nbytes, 8 * (hi - lo)),
+                                         "value": evals / dt2, "ms_per_step": dt2 / a.steps * 1e3, "ms_per_step_median": float(np.median(per2)) * 1e3}
+            out["gp_fit_ms"] = fit_ms
+            out["roofline"] = {"kernel": kernel_name + " (variance contraction V = L^-1 K*, fused column sum-of-squares)",
+                               "bound": "mfma", "achieved": ach, "peak": peak, "unit": "TOP/s (int8)" if a.i8 else "TFLOP/s", "frac": ach / peak,
+                               "traffic": traffic if not traffic_stale else None,
+                               "traffic_source": ("%s (rocprofv3 --pmc passes of this command, kernel %s, taken at git %s)" % (traffic_src, traffic_kernel, traffic_head)
+                                                  if traffic_src else None),
+                               "traffic_stale": traffic_stale,
+                               "launch_ms": gemm_ms, "algorithmic_flops_per_launch": gemm_flops,
+                               "other_kernels_ms_per_step": {k: v[0] / a.steps for k, v in ph2.items()}}
+            out["roofline_fit"] = roofline_fit
         if i8_block is not None:
             out["int8_variance_contraction"] = i8_block
-        if not a.no_cpu_baseline and world == 1:      # CPU baseline: rank 0 at N=1 only
+        if a.full and not a.no_cpu_baseline and world == 1:      # CPU baseline: rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(p, a, theta)
         print(json.dumps(out))
     if dist is not None:

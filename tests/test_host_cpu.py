@@ -203,6 +203,24 @@ def test_oracle_is_only_reachable_from_the_checker_legs():
     assert any(i > base for i in imports) and any(check < i < check + 200 for i in imports)
 
 
+def test_bench_plain_run_is_the_default(monkeypatch):
+    """bench.py: the extra measurements and the output dump are opt-in; --steps sets a positive number of timed steps."""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
 def test_synthetic_workload_is_the_oracles():
     from bocf_amd.synthetic import synthetic_problem
     from oracle import cpu_ref as R
