@@ -19,6 +19,7 @@ KERN_RBF, KERN_SE, KERN_MATERN52, KERN_MATERN32 = 0, 1, 2, 3
 ADD_NOISE, CLIP = 1, 2
 ACQ_EI, ACQ_PI = 0, 1
 UTIL_LINEAR, UTIL_NEG_SQ_DIST, UTIL_NEG_SUM_EXP, UTIL_NEG_EXP_COS, UTIL_ROSENBROCK = 0, 1, 2, 3, 4
+EU_MEAN, EU_CLOSED, EU_MC = 0, 1, 2
 
 _c_double_p = ctypes.POINTER(ctypes.c_double)
 _c_ll_p = ctypes.POINTER(ctypes.c_longlong)
@@ -67,6 +68,9 @@ SIGNATURES = {
     "bocf_acq_mc": (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int,
                                    _c_double_p, ctypes.c_int, _c_double_p]),
     "bocf_select_topk": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_ll_p, _c_double_p]),
+    "bocf_set_eu_samples": (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int, ctypes.c_int]),
+    "bocf_expected_utility": (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int,
+                                             ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, _c_double_p, _c_double_p]),
     "bocf_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "bocf_comm_init": (ctypes.c_int, [_ctx_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]),
     "bocf_comm_destroy": (ctypes.c_int, [_ctx_p]),

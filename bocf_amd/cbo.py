@@ -1,0 +1,235 @@
+"""The BOCF loop with the reference's surface (cbo.py:19-420: CBO) plus the evaluator it is driven by
+(GPyOpt/core/evaluators/sequential.py: Sequential).
+
+    bo = bocf_amd.CBO(model, space, objective, acquisition, bocf_amd.Sequential(acquisition), X_init, expectation_utility=psi)
+    bo.run_optimization(max_iter, results_file="results.txt")
+
+Every iteration does what the reference does, in the same order and with the same draws from np.random: the acquisition is
+optimised from the current recommendation (x_baseline = current_argmax), a repeated suggestion is perturbed, the objective is
+evaluated with noise, the model is updated, and the recommendation step (_current_max_value) solves one argmax problem per
+utility parameter -- here all of them in one batch on the device (bocf_amd.recommend) -- and records
+sum_l p_l U(theta_l, f(x_l)) in historical_optimal_values.  Elapsed times use time.perf_counter (the reference's time.clock no
+longer exists in Python 3).  Plotting, context variables, a non-constant cost and the convergence-assessment helpers are not
+provided: they raise NotImplementedError.
+"""
+import time
+
+import numpy as np
+
+from .acquisition_optimizer import ContextManager
+from .recommend import current_marginal_argmaxes
+
+
+class Sequential(object):
+    """GPyOpt/core/evaluators/sequential.py: one suggestion per iteration, from acquisition.optimize."""
+
+    def __init__(self, acquisition, batch_size=1):
+        self.acquisition = acquisition
+        self.batch_size = batch_size
+
+    def compute_batch(self, duplicate_manager=None, context_manager=None, x_baseline=None):
+        x, _ = self.acquisition.optimize(duplicate_manager=duplicate_manager, x_baseline=x_baseline)
+        return x
+
+
+class _ConstantCost(object):
+    """GPyOpt's CostModel(None): every evaluation costs the same; nothing to update."""
+    cost_type = "Constant cost"
+
+    def update_cost_model(self, x, cost_x):
+        pass
+
+
+def _zip(space, X):
+    return space.zip_inputs(X) if hasattr(space, "zip_inputs") else X
+
+
+def _unzip(space, X):
+    return space.unzip_inputs(X) if hasattr(space, "unzip_inputs") else X
+
+
+class CBO(object):
+    """cbo.py:19-58.  model: a bocf_amd.multi_outputGP; space: a Design_space; objective: a MultiObjective (or anything with
+    evaluate / evaluate_w_noise returning (list of m (n, 1) arrays, cost)); acquisition: a bocf_amd acquisition (its `utility` is
+    the loop's utility); evaluator: Sequential(acquisition); X_init (n, d); expectation_utility: the closed-form E[U] (psi) of the
+    recommendation step, or None (then the Monte-Carlo form, or the posterior mean for a linear utility)."""
+
+    def __init__(self, model, space, objective, acquisition, evaluator, X_init, Y_init=None, cost=None, normalize_Y=False,
+                 model_update_interval=1, expectation_utility=None):
+        if cost is not None:
+            raise NotImplementedError("only a constant evaluation cost is supported (cost=None)")
+        self.model = model
+        self.space = space
+        self.objective = objective
+        self.acquisition = acquisition
+        self.utility = acquisition.utility
+        self.expectation_utility = expectation_utility
+        self.evaluator = evaluator
+        self.X = X_init
+        self.Y = Y_init
+        self.normalize_Y = normalize_Y
+        self.cost = _ConstantCost()
+        self.model_update_interval = model_update_interval
+        self.historical_optimal_values = []
+        self.historical_time = []
+        self.n_attributes = self.model.output_dim
+        self.n_hyps_samples = min(10, self.model.number_of_hyps_samples())
+        self.n_parameter_samples = 10
+        self.full_parameter_support = self.utility.parameter_dist.use_full_support
+        self.n_starting, self.n_anchor = 200, 24        # GeneralOptimizer.optimize's defaults (general_optimizer.py:53)
+        self.context = None
+        self.current_argmax = np.atleast_2d(X_init[0, :])
+        self.last_recommendation = {}
+        self.verbosity = False
+
+    # ---- recommendation step -------------------------------------------------------------------------------------------------
+    def _recommend(self, parameters):
+        """argmax_x sum_h E_n[U(theta_l, f(x))] for every parameter row, in one batch; current_argmax becomes the last one."""
+        info = {}
+        X, _ = current_marginal_argmaxes(self.model, self.space, self.utility, parameters, self.expectation_utility,
+                                         n_hyps=self.n_hyps_samples, n_starting=self.n_starting, n_anchor=self.n_anchor, info=info)
+        self.last_recommendation = info
+        self.current_argmax = np.atleast_2d(X[-1])
+        return X
+
+    def _marginal_value(self, parameter, x):
+        """U(theta, f(x)) with the true (noiseless) objective at one recommended point."""
+        fx = np.reshape(self.objective.evaluate(np.atleast_2d(x))[0], (self.n_attributes,))
+        return self.utility.eval_func(parameter, fx)
+
+    def _parameters_of_this_step(self):
+        """(parameters, weights): the full support with its probabilities, or n_parameter_samples draws of parameter_dist.sample
+        (the first draw of the step) with None -- a plain mean."""
+        dist = self.utility.parameter_dist
+        if self.full_parameter_support:
+            return dist.support, dist.prob_dist
+        return dist.sample(self.n_parameter_samples), None
+
+    def _score(self, parameters, weights):
+        """sum_l w_l U(theta_l, f(x_l)) over the batched recommendations (a plain mean without weights), in parameter order."""
+        X = self._recommend(parameters)
+        terms = [self._marginal_value(parameters[l], X[l]) for l in range(len(parameters))]
+        total = 0
+        for l, t in enumerate(terms):
+            total = total + (t * weights[l] if weights is not None else t)
+        if weights is None:
+            total = total / len(parameters)
+        if self.verbosity:
+            print("recommended value %s" % (np.squeeze(total),))
+        return np.squeeze(total)
+
+    def _current_max_value(self):
+        """E_n[U(f(x_l))] over the utility parameters of this step (cbo.py:61-84)."""
+        return self._score(*self._parameters_of_this_step())
+
+    def _current_max_value_parallel(self):
+        """cbo.py:101-111 spreads the sampled parameters over a process pool; here they go through the same batched path, after the
+        same parameter draw."""
+        return self._score(self.utility.parameter_dist.sample(self.n_parameter_samples), None)
+
+    def _current_marginal_max_value(self, parameter):
+        return self._marginal_value(parameter, self._current_marginal_argmax(parameter))
+
+    def _current_marginal_argmax(self, parameter):
+        """argmax_x sum_h E_n[U(theta, f(x))] for one parameter (the batched path with L = 1); sets current_argmax."""
+        return np.atleast_2d(self._recommend(np.atleast_2d(np.asarray(parameter, dtype=float)))[0])
+
+    def _current_max_value_and_var(self):
+        raise NotImplementedError("_current_max_value_and_var (cbo.py:87-98) is not provided")
+
+    def convergence_assesment(self, *a, **kw):
+        raise NotImplementedError("the convergence assessment (cbo.py:423-460) plots; plotting is not provided")
+
+    def one_step_assesment(self, *a, **kw):
+        raise NotImplementedError("the one-step assessment (cbo.py:463-495) plots; plotting is not provided")
+
+    def integrated_plot(self, *a, **kw):
+        raise NotImplementedError("plotting is not provided")
+
+    plot_acquisition = plot_convergence = integrated_plot
+
+    # ---- the loop ------------------------------------------------------------------------------------------------------------
+    def run_optimization(self, max_iter=1, parallel=False, plot=False, results_file=None, max_time=np.inf, eps=1e-8, context=None,
+                         verbosity=False):
+        """Run max_iter acquisitions (or until max_time seconds have passed; None for either means no limit on it, both None
+        means no acquisition).  Per iteration: suggestion from x_baseline = current_argmax (perturbed if it repeats the previous
+        one), noisy evaluation, model update every model_update_interval acquisitions, recommendation step; then the results file."""
+        if self.objective is None:
+            raise ValueError("run_optimization needs an objective")
+        if plot:
+            raise NotImplementedError("plotting is not provided (plot=False)")
+        if context:
+            raise NotImplementedError("context variables are not provided (context=None)")
+        self.verbosity, self.results_file, self.context, self.eps = verbosity, results_file, context, eps
+        no_limit = max_iter is None and max_time is None
+        self.max_iter = 0 if no_limit else (np.inf if max_iter is None else max_iter)
+        self.max_time = np.inf if (no_limit or max_time is None) else max_time
+        if self.Y is None and self.X is not None:
+            self.Y = self.objective.evaluate(self.X)[0]
+        self.model.updateModel(self.X, self.Y)
+        self.time_zero = time.perf_counter()
+        self.cum_time, self.num_acquisitions = 0, 0
+        self.suggested_sample, self.Y_new = self.X, self.Y
+        while self.num_acquisitions < self.max_iter and self.cum_time < self.max_time:
+            self._one_iteration(parallel)
+        if results_file is not None:
+            self.save_results(results_file)
+
+    def _one_iteration(self, parallel):
+        previous = self.suggested_sample
+        x = self.compute_next_evaluations()
+        self.suggested_sample = self._perturb(x) if np.all(x == previous) else x
+        try:
+            # the reference calls update_Z_samples() without its required argument: the TypeError is swallowed, nothing is drawn
+            self.acquisition.update_Z_samples()
+        except Exception:
+            pass
+        self.X = np.vstack((self.X, self.suggested_sample))
+        self.evaluate_objective()
+        if self.num_acquisitions % self.model_update_interval == 0:
+            self._update_model()
+        self.model.get_model_parameters_names()
+        self.model.get_model_parameters()
+        use_parallel = parallel and not self.full_parameter_support
+        value = self._current_max_value_parallel() if use_parallel else self._current_max_value()
+        self.historical_optimal_values.append(value)
+        self.cum_time = time.perf_counter() - self.time_zero
+        self.historical_time.append(self.cum_time)
+        self.num_acquisitions += 1
+        if self.verbosity:
+            print("iteration %d: x = %s, recommended value %s, %.2f s" % (self.num_acquisitions, self.suggested_sample, value, self.cum_time))
+
+    def evaluate_objective(self):
+        """Noisy observation at the suggestion, appended to every output's column."""
+        self.Y_new, cost = self.objective.evaluate_w_noise(self.suggested_sample)
+        self.cost.update_cost_model(self.suggested_sample, cost)
+        self.Y = [np.vstack((old, new)) for old, new in zip(self.Y, self.Y_new)]
+
+    def _distance_last_evaluations(self):
+        return float(np.linalg.norm(self.X[-1] - self.X[-2]))
+
+    def _perturb(self, x):
+        """x moved by N(0, 0.01^2) noise per coordinate (rounded to the space), redrawn until it differs from x."""
+        while True:
+            moved = self.space.round_optimum(x + np.random.normal(size=x.shape, scale=1e-2))
+            if not np.all(moved == x):
+                return moved
+
+    def compute_next_evaluations(self, pending_zipped_X=None, ignored_zipped_X=None):
+        """The next suggestion: update the model (with learned hyper-parameters this re-runs the sampler, as the reference does),
+        then optimise the acquisition starting from x_baseline = current_argmax."""
+        if self.Y is None and self.X is not None:
+            self.Y = self.objective.evaluate(self.X)[0]
+        self.model.updateModel(self.X, self.Y)
+        self.acquisition.optimizer.context_manager = ContextManager(self.space, self.context)
+        return _zip(self.space, self.evaluator.compute_batch(duplicate_manager=None, x_baseline=self.current_argmax))
+
+    def _update_model(self):
+        self.model.updateModel(_unzip(self.space, self.X), list(self.Y))
+
+    def get_evaluations(self):
+        return self.X.copy(), [y.copy() for y in self.Y]
+
+    def save_results(self, filename):
+        """Two columns per iteration: the recommended value and the elapsed seconds."""
+        np.savetxt(filename, np.column_stack((np.atleast_1d(self.historical_optimal_values), np.atleast_1d(self.historical_time))))

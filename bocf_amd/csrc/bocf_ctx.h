@@ -159,6 +159,13 @@ struct bocf_ctx {
   int S_mc = 0;
   bool have_acq = false;
   DevBuf blk_idx, blk_val, out_idx, out_val;
+  // ---- expected utility of the recommendation step (bocf_set_eu_samples / bocf_expected_utility): buffers of its own, so the
+  // acquisition state above (acq, dacq, theta / prob / params, Wt, the best-so-far cache) is left as it was
+  DevBuf eu_theta, eu_rows, eu_Z, eu_val, eu_grad;
+  int eu_S = 0, eu_L = 0, eu_m = 0;  // samples per parameter, parameters and outputs per hyper-sample of eu_Z (eu_S = 0: none set)
+  void* eu_pin = nullptr;            // pinned staging of theta | params | rows
+  size_t eu_pin_cap = 0;
+  hipEvent_t ev_eu_pin = nullptr;    // the upload out of eu_pin
   // ---- profiling of the dominant kernel
   bool profile = false;
   double test_diag_shift = 0.0;

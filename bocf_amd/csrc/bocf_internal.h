@@ -323,6 +323,26 @@ void launch_acq_linear(const AcqArgs& a, hipStream_t s);
 void launch_acq_mc(const AcqArgs& a, hipStream_t s);
 void launch_acq_linear_grad(const AcqArgs& a, hipStream_t s);
 void launch_acq_mc_grad(const AcqArgs& a, hipStream_t s);
+// ---------------------------------------------------------------------------------------
+// expected utility of the recommendation step (eu.hip)
+// ---------------------------------------------------------------------------------------
+struct EuArgs {
+  const double* mean; const double* var; long ld;   // (m, ld) rows of one hyper-sample, first C columns valid (var unused in MEAN mode)
+  const double* dmean; const double* dvar; long ldg; int d;   // (m, ldg, d); read only when grad != nullptr
+  int m, C;
+  int mode;                // BOCF_EU_*
+  int util_kind;           // BOCF_UTIL_*
+  int theta_dim;
+  const double* theta;     // device (L, theta_dim)
+  const int* rows;         // device (C): parameter index of every candidate, in [0, L)
+  const double* util_params;
+  const double* Zt; int S; // device (L, m, S): transposed normals of every parameter (MC mode)
+  double* val;             // device (C)
+  double* grad;            // device (C, d) or nullptr (value only)
+  int accumulate;          // 0: val/grad are written; 1: added to (hyper-sample h > 0)
+  double scale;            // n_hyps with one resident hyper-sample, else 1
+};
+void launch_eu(const EuArgs& a, hipStream_t s);
 // two-stage top-k (value desc, index asc); out: idx (k) int64, val (k)
 void launch_topk(const double* acq, int C, int k, long long* blk_idx, double* blk_val, long long* out_idx, double* out_val, hipStream_t s);
 int topk_num_blocks(int C);

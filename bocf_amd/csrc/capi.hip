@@ -95,10 +95,12 @@ extern "C" void bocf_destroy(bocf_ctx* c) {
   if (c->fit_pin) (void)hipHostFree(c->fit_pin);
   if (c->up_pin) (void)hipHostFree(c->up_pin);
   if (c->ev_pin) (void)hipEventDestroy(c->ev_pin);
+  if (c->eu_pin) (void)hipHostFree(c->eu_pin);
+  if (c->ev_eu_pin) (void)hipEventDestroy(c->ev_eu_pin);
   DevBuf* bufs[] = {&c->R32, &c->Ri8, &c->Ri8e, &c->Ki8, &c->Ki8e, &c->X, &c->Xs, &c->S, &c->R, &c->RT, &c->E, &c->ET, &c->T, &c->yc, &c->tvec, &c->alpha, &c->lml, &c->jit, &c->hypd,
                     &c->info, &c->mu_train, &c->rvec, &c->dvec, &c->hmc_buf, &c->Xc, &c->Kstar, &c->meanpart, &c->sumsq, &c->mean, &c->var, &c->acq, &c->Vbuf, &c->dmean, &c->dvar, &c->dacq, &c->Vs, &c->Ws, &c->theta,
                     &c->prob, &c->best, &c->params, &c->Wt, &c->blk_idx, &c->blk_val, &c->out_idx, &c->out_val, &c->gpart, &c->gout, &c->pack, &c->gidx,
-                    &c->gval, &c->shard_meta, &c->chol_flags};
+                    &c->gval, &c->shard_meta, &c->chol_flags, &c->eu_theta, &c->eu_rows, &c->eu_Z, &c->eu_val, &c->eu_grad};
   for (DevBuf* b : bufs) b->release();
   if (c->infer_out) (void)hipHostFree(c->infer_out);
   for (hipEvent_t ev : c->ev_parts) (void)hipEventDestroy(ev);
@@ -167,7 +169,7 @@ static const OptDesc g_options[] = {
     {"swizzle", -1, 258, 0, [](bocf_ctx* c, long long v) { c->swizzle = (int)v; }, opt_swizzle_ok, "variance-GEMM tiling: -1 by size, 0 128-row tiles, 258 256-row tiles (probes build: also 1, 100..163, 256, 257)"},
     {"hyper_samples", 1, 64, 1,
      [](bocf_ctx* c, long long v) {
-       if ((int)v != c->hyper_samples) c->S_mc = 0;   // the transposed normals are laid out per group size
+       if ((int)v != c->hyper_samples) c->S_mc = c->eu_S = 0;   // the transposed normals are laid out per group size
        c->hyper_samples = (int)v;
      },
      nullptr, "the fitted outputs are H hyper-samples x m / H model outputs"},
@@ -248,6 +250,7 @@ extern "C" int bocf_set_posterior(bocf_ctx* c, int m, int C, int N, const double
   c->canned = true;
   c->have_acq = false;
   c->S_mc = 0;
+  c->eu_S = 0;
   return 0;
 }
 
@@ -670,25 +673,30 @@ static int group_size(bocf_ctx* c, const char* where) {
   return c->m / H;
 }
 
-// acquisition values (and gradients) to the host: small batches through the pinned buffer -- both copies asynchronous, one synchronisation
-static int finish_acq(bocf_ctx* c, double* acq_out, double* dacq_out = nullptr) {
-  c->have_acq = true;
-  const size_t b0 = acq_out ? sizeof(double) * (size_t)c->C : 0, b1 = dacq_out ? sizeof(double) * (size_t)c->C * c->d : 0;
+// two device vectors to the host: small totals through the pinned buffer -- both copies asynchronous, one synchronisation
+static int copy_pair_out(bocf_ctx* c, const void* src0, double* out0, size_t b0, const void* src1, double* out1, size_t b1) {
   if (b0 + b1 > 0 && b0 + b1 <= BOCF_PIN_BYTES && pin_ensure(&c->pin_out, &c->pin_out_cap, b0 + b1) == 0) {
     char* pin = static_cast<char*>(c->pin_out);
-    if (b0) HIPCHK(hipMemcpyAsync(pin, c->acq.p, b0, hipMemcpyDeviceToHost, c->stream));
-    if (b1) HIPCHK(hipMemcpyAsync(pin + b0, c->dacq.p, b1, hipMemcpyDeviceToHost, c->stream));
+    if (b0) HIPCHK(hipMemcpyAsync(pin, src0, b0, hipMemcpyDeviceToHost, c->stream));
+    if (b1) HIPCHK(hipMemcpyAsync(pin + b0, src1, b1, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (b0) memcpy(acq_out, pin, b0);
-    if (b1) memcpy(dacq_out, pin + b0, b1);
+    if (b0) memcpy(out0, pin, b0);
+    if (b1) memcpy(out1, pin + b0, b1);
     LAUNCHCHK();
     return 0;
   }
-  if (dacq_out) HIPCHK(hipMemcpyAsync(dacq_out, c->dacq.p, b1, hipMemcpyDeviceToHost, c->stream));
-  if (acq_out) HIPCHK(hipMemcpyAsync(acq_out, c->acq.p, b0, hipMemcpyDeviceToHost, c->stream));
+  if (out1) HIPCHK(hipMemcpyAsync(out1, src1, b1, hipMemcpyDeviceToHost, c->stream));
+  if (out0) HIPCHK(hipMemcpyAsync(out0, src0, b0, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   LAUNCHCHK();
   return 0;
+}
+
+// acquisition values (and gradients) to the host
+static int finish_acq(bocf_ctx* c, double* acq_out, double* dacq_out = nullptr) {
+  c->have_acq = true;
+  const size_t b0 = acq_out ? sizeof(double) * (size_t)c->C : 0, b1 = dacq_out ? sizeof(double) * (size_t)c->C * c->d : 0;
+  return copy_pair_out(c, c->acq.p, acq_out, b0, c->dacq.p, dacq_out, b1);
 }
 
 // The reference's h-loop (maEI.py:85-97, uEI_noiseless.py:71-82) runs here: hyper-sample h reads rows
@@ -827,6 +835,100 @@ extern "C" int bocf_acq_mc_grad(bocf_ctx* c, int util_kind, const double* util_p
   a.dmean = c->dmean.as<double>(); a.dvar = c->dvar.as<double>(); a.ldg = c->pred_cap; a.d = c->d; a.dacq = c->dacq.as<double>();
   if (acq_over_hyper_samples(c, a, m, 0, launch_acq_mc_grad)) return -1;
   return finish_acq_grad(c, acq_out, dacq_out);
+}
+
+extern "C" int bocf_set_eu_samples(bocf_ctx* c, const double* Z, int L, int S) {
+  if (!c || !c->fitted || !Z || L < 1 || S < 1) return fail("bocf_set_eu_samples", "model not fitted / bad samples");
+  HIPCHK(hipSetDevice(c->device));
+  const int m = group_size(c, "bocf_set_eu_samples");     // Z is (L, S, outputs per hyper-sample)
+  if (m < 0) return -1;
+  std::vector<double> zt((size_t)L * m * S);               // -> (L, m, S): lanes of a wave read consecutive samples
+  for (int l = 0; l < L; ++l)
+    for (int s = 0; s < S; ++s)
+      for (int j = 0; j < m; ++j) zt[((size_t)l * m + j) * S + s] = Z[((size_t)l * S + s) * m + j];
+  if (c->eu_Z.ensure(sizeof(double) * zt.size())) return -1;
+  HIPCHK(hipMemcpyAsync(c->eu_Z.p, zt.data(), sizeof(double) * zt.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->eu_L = L;
+  c->eu_S = S;
+  c->eu_m = m;
+  return 0;
+}
+
+extern "C" int bocf_expected_utility(bocf_ctx* c, int mode, int util_kind, const double* util_params, int n_util_params, const double* theta,
+                                     int theta_dim, int L, const int* row_param, int n_hyps, double* val_out, double* grad_out) {
+  const char* me = "bocf_expected_utility";
+  if (!c || !c->fitted) return fail(me, "model not fitted");
+  if (c->canned) return fail(me, "the context holds a host-given posterior (bocf_set_posterior): fit first");
+  if (mode < BOCF_EU_MEAN || mode > BOCF_EU_MC) return fail(me, "unknown mode");
+  if (util_kind < 0 || util_kind > BOCF_UTIL_ROSENBROCK) return fail(me, "unknown utility kind");
+  const int m = group_size(c, me);
+  if (m < 0) return -1;
+  if (L < 1 || theta_dim < 1 || !theta) return fail(me, "theta must be (L >= 1, theta_dim >= 1)");
+  if ((mode == BOCF_EU_MEAN || util_kind == BOCF_UTIL_LINEAR || util_kind == BOCF_UTIL_NEG_SQ_DIST) && theta_dim != m)
+    return fail(me, "theta_dim must equal m");
+  if (mode != BOCF_EU_MEAN && util_kind == BOCF_UTIL_ROSENBROCK && (m & 1)) return fail(me, "rosenbrock utility needs even m");
+  if (mode == BOCF_EU_CLOSED && (util_kind == BOCF_UTIL_LINEAR || util_kind == BOCF_UTIL_NEG_EXP_COS))
+    return fail(me, "no closed-form expectation for this utility (use the Monte-Carlo mode)");
+  if (mode == BOCF_EU_MC && util_kind == BOCF_UTIL_NEG_EXP_COS && n_util_params != m) return fail(me, "neg_exp_cos needs m weights");
+  if (n_util_params < 0 || n_util_params > BOCF_MAX_M || (n_util_params > 0 && !util_params)) return fail(me, "bad utility parameters");
+  if (mode == BOCF_EU_MC && c->eu_S < 1) return fail(me, "no Monte-Carlo samples set (bocf_set_eu_samples)");
+  if (mode == BOCF_EU_MC && c->eu_L < L) return fail(me, "fewer Monte-Carlo sample blocks than parameters");
+  if (mode == BOCF_EU_MC && c->eu_m != m) return fail(me, "the Monte-Carlo samples were set for another output count");
+  if (grad_out && c->d > 64) return fail(me, "input dimension too large");
+  if (n_hyps < 1) return fail(me, "n_hyps must be >= 1");
+  if (c->hyper_samples > 1 && n_hyps > c->hyper_samples) return fail(me, "n_hyps exceeds the resident hyper-samples");
+  HIPCHK(hipSetDevice(c->device));
+  const int C = c->C, d = c->d;
+  if (C == 0) return 0;
+  if (!val_out || !row_param) return fail(me, "null output / row_param");
+  for (int i = 0; i < C; ++i)
+    if (row_param[i] < 0 || row_param[i] >= L) return fail(me, "row_param out of range [0, L)");
+  // theta | params | rows in one pinned staging buffer (free again once the previous call's copy is done)
+  const size_t bt = sizeof(double) * (size_t)L * theta_dim, bp = sizeof(double) * BOCF_MAX_M, br = sizeof(int) * (size_t)C;
+  if (c->eu_theta.ensure(bt + bp) || c->eu_rows.ensure(br) || c->eu_val.ensure(sizeof(double) * (size_t)C) ||
+      (grad_out && c->eu_grad.ensure(sizeof(double) * (size_t)C * d)))
+    return -1;
+  if (c->ev_eu_pin) HIPCHK(hipEventSynchronize(c->ev_eu_pin));       // (only pending when an earlier call failed before its synchronisation)
+  else HIPCHK(hipEventCreateWithFlags(&c->ev_eu_pin, hipEventDisableTiming));
+  const bool pinned = pin_ensure(&c->eu_pin, &c->eu_pin_cap, bt + bp + br) == 0;
+  std::vector<char> pageable;
+  char* stage;
+  if (pinned) {
+    stage = static_cast<char*>(c->eu_pin);
+  } else {
+    pageable.resize(bt + bp + br);
+    stage = pageable.data();
+  }
+  memcpy(stage, theta, bt);
+  memset(stage + bt, 0, bp);
+  if (n_util_params > 0) memcpy(stage + bt, util_params, sizeof(double) * n_util_params);
+  memcpy(stage + bt + bp, row_param, br);
+  HIPCHK(hipMemcpyAsync(c->eu_theta.p, stage, bt + bp, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->eu_rows.p, stage + bt + bp, br, hipMemcpyHostToDevice, c->stream));
+  if (pinned) HIPCHK(hipEventRecord(c->ev_eu_pin, c->stream));
+  else HIPCHK(hipStreamSynchronize(c->stream));
+  // predict_noiseless (gpmodel.py:151-159): no likelihood noise, clipped; the mean form needs no variance unless gradients are asked for
+  const bool need_grad = grad_out != nullptr;
+  if (run_predict(c, BOCF_CLIP, mode != BOCF_EU_MEAN || need_grad, need_grad)) return -1;
+  const int H = c->hyper_samples;
+  const int nh = H == 1 ? 1 : n_hyps;
+  EuArgs a{};
+  a.ld = c->pred_cap; a.ldg = c->pred_cap; a.d = d;
+  a.m = m; a.C = C; a.mode = mode; a.util_kind = util_kind; a.theta_dim = theta_dim;
+  a.theta = c->eu_theta.as<double>(); a.util_params = c->eu_theta.as<double>() + (size_t)L * theta_dim;
+  a.rows = c->eu_rows.as<int>(); a.Zt = c->eu_Z.as<double>(); a.S = c->eu_S;
+  a.val = c->eu_val.as<double>(); a.grad = need_grad ? c->eu_grad.as<double>() : nullptr;
+  a.scale = H == 1 ? (double)n_hyps : 1.0;
+  for (int h = 0; h < nh; ++h) {
+    a.mean = c->mean.as<double>() + (size_t)h * m * a.ld;
+    a.var = c->var.as<double>() + (size_t)h * m * a.ld;
+    if (need_grad) { a.dmean = c->dmean.as<double>() + (size_t)h * m * a.ldg * d; a.dvar = c->dvar.as<double>() + (size_t)h * m * a.ldg * d; }
+    a.accumulate = h > 0;
+    PhaseTimer t(c, "eu");
+    launch_eu(a, c->stream);
+  }
+  return copy_pair_out(c, c->eu_val.p, val_out, sizeof(double) * (size_t)C, c->eu_grad.p, grad_out, need_grad ? sizeof(double) * (size_t)C * d : 0);
 }
 
 extern "C" int bocf_select_topk(bocf_ctx* c, int k, long long* idx_out, double* val_out) {

@@ -116,8 +116,10 @@ class multi_outputGP(object):
         self._Y = None
         self._fitted = False
         self._cand_token = None
+        self._n_resident = None       # candidates resident on the device (unknown after a fit)
         self._fit_key = None
         self._W_key = None
+        self._Z_key = None
         self.incremental = True       # O(N^2) updateModel when only targets change or one observation is appended
         # ---- hyper-parameter learning (fixed_hyps=False): GPModel's sampler settings (gpmodel.py:32)
         self.n_burnin, self.subsample_interval, self.step_size, self.leapfrog_steps, self.max_iters = 100, 10, 1e-1, 20, 200
@@ -148,7 +150,9 @@ class multi_outputGP(object):
         st["_ctx"] = None
         st["_fitted"] = False
         st["_cand_token"] = None
+        st["_n_resident"] = None
         st["_W_key"] = None
+        st["_Z_key"] = None
         st["_query_cache"] = st["_grad_cache"] = None
         st["_ibuf"] = None
         return st
@@ -180,6 +184,7 @@ class multi_outputGP(object):
         if len(Y) != self.output_dim or any(y.shape[0] != X.shape[0] for y in Y):
             raise ValueError("Y_all must hold output_dim arrays of N observations")
         prevX = self._X
+        self._n_resident = None
         self._X, self._Y = X.copy(), [y[:, None].copy() for y in Y]
         self._Ymat = None
         self._ibuf = None
@@ -251,7 +256,9 @@ class multi_outputGP(object):
         _ffi.check(rc, "bocf_fit")
         self._fitted = False
         self._W_key = None
+        self._Z_key = None
         self._cand_token = None
+        self._n_resident = None       # candidates resident on the device (unknown after a fit)
         if rc > 0:   # jitchol gave up (GPy/util/linalg.py:71) for the outputs whose last rung still has a bad pivot
             err = np.linalg.LinAlgError("not positive definite, even with jitter.")
             err.outputs = self._failed_outputs(M)
@@ -340,7 +347,9 @@ class multi_outputGP(object):
         _ffi.check(rc, "bocf_infer")
         self._fitted = False
         self._W_key = None
+        self._Z_key = None
         self._cand_token = None
+        self._n_resident = None       # candidates resident on the device (unknown after a fit)
         if rc > 0:   # jitchol gave up (GPy/util/linalg.py:71) for the outputs whose last rung still has a bad pivot
             err = np.linalg.LinAlgError("not positive definite, even with jitter.")
             err.outputs = self._failed_outputs(self.output_dim)
@@ -427,7 +436,9 @@ class multi_outputGP(object):
             _ffi.check(rc, "bocf_hmc_streamed")
         self._fitted = False
         self._W_key = None
+        self._Z_key = None
         self._cand_token = None
+        self._n_resident = None       # candidates resident on the device (unknown after a fit)
         for j, o in enumerate(outs):
             o.param_array[:] = theta[j]
         out_chains = [chains[j, :, :int(np.sum(~outs[j].fixed))].copy() for j in range(m)]
@@ -469,7 +480,9 @@ class multi_outputGP(object):
         X = _ffi.f64(X)
         if X.ndim != 2 or X.shape[1] != self._X.shape[1]:
             raise ValueError("candidates must be (n, %d)" % self._X.shape[1])
+        self._n_resident = None
         _ffi.check(_ffi.load().bocf_set_candidates(self._context().handle, _ffi.dptr(X), X.shape[0]), "bocf_set_candidates")
+        self._n_resident = X.shape[0]
         return X.shape[0]
 
     def _predict(self, X, flags, want_var=True):
@@ -724,6 +737,83 @@ class multi_outputGP(object):
             _ffi.check(lib.bocf_acq_mc(ctx.handle, kind, util_kind, _ffi.dptr(params), 0 if params is None else params.size, _ffi.dptr(th),
                                        tdim, _ffi.dptr(prob), L, _ffi.dptr(acq)), "bocf_acq_mc")
         return acq
+
+    def set_eu_samples(self, Z):
+        """Upload the Monte-Carlo normals of the recommendation step, Z (L, S, output_dim): block l is the np.random.normal(size=(S, m))
+        the reference draws for parameter l (cbo.py:200).  Key-cached like set_mc_samples: an L-BFGS run re-sends the same Z."""
+        self._ensure_fitted()
+        Z = _ffi.f64(Z)
+        if Z.ndim == 2:
+            Z = Z[None]
+        if Z.ndim != 3 or Z.shape[2] != self.output_dim:
+            raise ValueError("Z must be (L, S, output_dim)")
+        key = (Z.shape, hash(Z.tobytes()))
+        if key == self._Z_key:
+            return
+        _ffi.check(_ffi.load().bocf_set_eu_samples(self._context().handle, _ffi.dptr(Z), Z.shape[0], Z.shape[1]), "bocf_set_eu_samples")
+        self._Z_key = key
+
+    def expected_utility(self, X, mode, utility, thetas, row_param, Z=None, n_hyps=None, grad=False, util_params=None):
+        """Posterior expected utility of the recommendation step (cbo.py:121-235) on the device, all utility parameters in one call:
+        row i of X takes parameter thetas[row_param[i]] and gets
+
+            v_i = sum_{h < n_hyps} E_h[ U(theta, f(X_i)) ]      (a sum, not a mean: cbo.py:160)
+
+        under the noiseless posterior (predict_noiseless).  `mode`: "mean" (theta . mu, utility.linear), "closed" (the closed-form
+        expectation of the device utility) or "mc" (sum over the S normals Z[row_param[i]] of U(theta, mu + sigma o Z_s)); or the
+        _ffi.EU_* value.  `utility`: a Utility with a device kind, a device utility name or its _ffi.UTIL_* value (ignored in "mean"
+        mode); `util_params` overrides utility.device_params.  Z (L, S, m) is needed in "mc" mode (cached on the device).
+        X = None evaluates the candidates already resident (the last batch of any device call); row_param must then hold exactly
+        one index per resident candidate (ValueError otherwise).
+        n_hyps: hyper-samples to sum (default min(10, number_of_hyps_samples())); more than are resident is an IndexError; with fixed
+        hyper-parameters the one resident sample counts n_hyps times, as the reference's identical passes do.  thetas must be 2-D.  Leaves the model on hyper-sample n_hyps - 1, as the
+        reference's set_hyperparameters(h) loop does.  Returns v (n,), or (v (n,), dv/dX (n, d)) with grad=True."""
+        modes = {"mean": _ffi.EU_MEAN, "closed": _ffi.EU_CLOSED, "mc": _ffi.EU_MC}
+        mode = modes[mode] if isinstance(mode, str) else int(mode)
+        self._ensure_fitted()
+        if hasattr(utility, "device_kind"):
+            kind = 0 if mode == _ffi.EU_MEAN else utility.device_kind(self.output_dim)
+            if util_params is None:
+                util_params = utility.device_params
+        elif isinstance(utility, str):
+            from .utility import _DEVICE_KINDS
+            kind = _DEVICE_KINDS[utility]
+        else:
+            kind = 0 if utility is None else int(utility)
+        n_h = min(10, self.number_of_hyps_samples()) if n_hyps is None else int(n_hyps)
+        if n_h < 1:
+            raise ValueError("n_hyps must be >= 1")
+        if not self.fixed_hyps and n_h > self._H:
+            # the reference's set_hyperparameters(h) loop would fail on h >= H: no silent clamping
+            raise IndexError("n_hyps = %d exceeds the %d resident hyper-samples" % (n_h, self._H))
+        th = _ffi.f64(thetas)
+        if th.ndim != 2:
+            raise ValueError("thetas must be 2-D (L, theta_dim); write L scalar parameters as an (L, 1) array")
+        L, tdim = th.shape
+        rows = np.ascontiguousarray(np.asarray(row_param).reshape(-1), dtype=np.int32)
+        if mode == _ffi.EU_MC:
+            if Z is None:
+                raise ValueError("the Monte-Carlo mode needs Z (L, S, output_dim)")
+            self.set_eu_samples(Z)
+        if X is not None:
+            n = self._set_candidates(np.atleast_2d(X))
+            if n != rows.size:
+                raise ValueError("row_param must hold one parameter index per row of X")
+        elif self._n_resident is None or self._n_resident != rows.size:
+            # the library reads row_param and writes the outputs for every RESIDENT candidate: the sizes must agree
+            raise ValueError("X = None evaluates the resident candidates (%s): row_param must hold one index per candidate, it holds %d"
+                             % ("none known" if self._n_resident is None else self._n_resident, rows.size))
+        n = rows.size
+        params = None if util_params is None else _ffi.f64(np.atleast_1d(util_params))
+        val = np.empty(n)
+        dval = np.empty((n, self._X.shape[1])) if grad else None
+        if n:
+            _ffi.check(_ffi.load().bocf_expected_utility(self._context().handle, mode, kind, _ffi.dptr(params), 0 if params is None else params.size,
+                                                         _ffi.dptr(th), tdim, L, rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), n_h,
+                                                         _ffi.dptr(val), _ffi.dptr(dval)), "bocf_expected_utility")
+        if not self.fixed_hyps:
+            self._current_h = min(n_h, self._H) - 1
+        return (val, dval) if grad else val
 
     def select_topk(self, k):
         """(indices, values) of the k best candidates of the last acquisition call -- the

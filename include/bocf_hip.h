@@ -283,6 +283,32 @@ int bocf_acq_mc_grad(bocf_ctx* ctx, int util_kind, const double* util_params, in
  * idx_out (k) int64, val_out (k) or NULL. */
 int bocf_select_topk(bocf_ctx* ctx, int k, long long* idx_out, double* val_out);
 
+/* ---- expected utility of the recommendation step (cbo.py:121-235, CBO._current_marginal_argmax).  The reference maximises, for
+ * every utility parameter theta_l of _current_max_value (cbo.py:61-84), the posterior expected utility
+ *   v(x) = sum_{h < n_hyps} E_h[ U(theta_l, f(x)) ]          (a SUM over hyper-samples and samples, cbo.py:160 "not normalized")
+ * with the posterior of predict_noiseless (no likelihood noise, variance clipped at 1e-10).  Modes:
+ *   BOCF_EU_MEAN    theta . mu                    utility.linear (cbo.py:124-157); util_kind ignored, theta_dim = m
+ *   BOCF_EU_CLOSED  psi(theta, mu, var)           expectation_utility given (cbo.py:159-188); closed forms of
+ *                   NEG_SQ_DIST  -||mu - theta||^2 - sum var
+ *                   NEG_SUM_EXP  -sum exp(mu_j + var_j / 2)
+ *                   ROSENBROCK   -sum_{j<m/2} (a - mu_j)^2 + 100 mu_{j+m/2}^2 + var_j + 100 var_{j+m/2}
+ *                   (LINEAR and NEG_EXP_COS have none here: an error)
+ *   BOCF_EU_MC      sum_{s<S} U(theta, mu + sigma o Z_s)   otherwise (cbo.py:190-231); Z of bocf_set_eu_samples, per parameter
+ * Hyper-samples: with several resident (option hyper_samples = H > 1) the first n_hyps <= H are summed; with one (fixed
+ * hyper-parameters, where the reference makes n_hyps identical passes) the value is multiplied by n_hyps. */
+enum { BOCF_EU_MEAN = 0, BOCF_EU_CLOSED = 1, BOCF_EU_MC = 2 };
+
+/* Upload the Monte-Carlo normals of the recommendation step: Z (L,S,m), block l = the np.random.normal(size=(S, m)) drawn for
+ * parameter l (cbo.py:200).  Independent of bocf_set_mc_samples. */
+int bocf_set_eu_samples(bocf_ctx* ctx, const double* Z, int L, int S);
+
+/* Expected utility (and its input gradient) over the resident candidates, candidate c taking parameter row_param[c] in [0, L) of
+ * theta (L,theta_dim): all L argmax problems in one call.  val_out (C); grad_out (C,d) or NULL (value only: no gradient pass).
+ * Leaves the acquisition state (the last acquisition vector for bocf_select_topk, the Monte-Carlo samples of bocf_set_mc_samples,
+ * the best-so-far cache) untouched. */
+int bocf_expected_utility(bocf_ctx* ctx, int mode, int util_kind, const double* util_params, int n_util_params, const double* theta,
+                          int theta_dim, int L, const int* row_param, int n_hyps, double* val_out, double* grad_out);
+
 /* ---- multi-GPU: candidate shards, ONE collective.  One process per GPU, one context per process.  The
  * reference's own candidate parallelism is a pathos process pool over single candidates (uEI_noiseless.py:85-97); here rank
  * r scores the contiguous slice [lo_r, hi_r) of the batch against its resident fit and the ranks exchange only their k
