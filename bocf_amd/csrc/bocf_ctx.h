@@ -1,6 +1,7 @@
 // Context of one GPU (opaque bocf_ctx of include/bocf_hip.h) and the error plumbing shared by capi.hip and comm.hip.
 #pragma once
 #include "bocf_internal.h"
+#include "chol_plan.h"
 #include "../../include/bocf_hip.h"
 
 #include <map>
@@ -11,7 +12,8 @@
 int bocf_fail(const char* what, const char* detail);      // records bocf_last_error(), returns -1
 void bocf_set_error(const char* text);                    // records bocf_last_error() verbatim (positive LAPACK-style returns)
 int bocf_launch_status();
-int bocf_run_cholesky(bocf_ctx* c);                       // capi_chol.hip: blocked Cholesky of all outputs, schedule by size / option
+int bocf_plan_cholesky(bocf_ctx* c, CholPlan* out);       // capi_chol.hip: the schedule of the next factorization, its streams and counters
+int bocf_run_cholesky(bocf_ctx* c, const CholPlan* plan = nullptr);   // blocked Cholesky of all outputs (nullptr: planned here)
 int bocf_run_trtri(bocf_ctx* c, bool early_done);         // capi_chol.hip: R = U^-1 (the part the factorization did not already start)
 int bocf_comm_broadcast(bocf_ctx* c, double* buf, size_t count, int root);   // comm.hip: ncclBroadcast on the context's stream
 int bocf_comm_group(bool start);                                             // ncclGroupStart / ncclGroupEnd
@@ -81,27 +83,18 @@ struct bocf_ctx {
   // holds `res_cus` compute units that NO other stream of the factorization may use (the trailing updates run on streams
   // masked to the complement), so a diagonal block never waits for a CU to drain and never shares one.
   hipStream_t s_res = nullptr, s_hi = nullptr, s_bulk = nullptr;
-  DevBuf chol_flags;         // device-side dependency counters of the reserved-CU schedule (+ the timeout word)
+  DevBuf chol_flags;         // device-side dependency counters of the gated schedules (+ the timeout word)
   int chol_flags_used = 0;
-  int chol_err_off = 0;      // index of the time-out word inside chol_flags (set by the schedule that used them)
-  int team_fit = -1;         // one-launch factorization + inverse by resident workgroup teams (chol_team.hip): -1 = by size (2..24 panels), 0 / 1 = never / whenever it applies
-  int team_panels = 6;       // panels per team launch where teams work in groups (the first block rows of the hybrid schedule; team_fit = 1 without hybrid), each followed by ONE trailing update with K = 128 x that
+  int chol_err_off = 0;      // index of the time-out word inside chol_flags (from the plan of the last factorization)
+  CholOptions chol;          // the factorization-schedule options (chol_plan.h)
   int flags_device_zeroed = 0;   // the caller's kernels zero the team schedule's counters in front of every factorization (stream-resident HMC)
   int want_kinv = 0;         // the caller is an INFERENCE (bocf_lml_gradients follows): a schedule that can, leaves Ky^-1 in the T scratch
   int kinv_done = 0;         // ... and did
-  int team_hybrid = 2;       // more than team_whole_max panels: the first block rows by team launches of team_panels panels + trailing updates (1: by the launched schedule), ONE team launch (Cholesky + inverse) for the rest; 0: team_fit = 1 means panel groups throughout
-  int team_tail_share = 5;   // hybrid schedule: eighths of the compute units the tail's teams take (the rest is for the early inverse underneath)
-  int team_whole_max = 24;   // panels up to which ONE team launch factors and inverts everything (beyond: the hybrid schedule)
-  int team_crit_load = 4;    // teams: the workgroups that stream the critical units carry nothing else while the others get by with <= this many units each
-  int team_stream = 1;       // teams: U[p][p+1] and the last row of A[p+1][p+1] are formed 16 rows at a time underneath potrf(p) by a workgroup of their own
   int inverse_done = 0;      // the factorization schedule already produced R and R^T (team schedule)
-  int ncu = 0;               // compute units of the device (read once)
+  int ncu = 0;               // compute units of the device (read once, by bocf_create)
   unsigned long long* team_tl = nullptr;   // probes build: task timeline of the team kernel (tools/team_timeline.py)
   int res_cus = 0;           // CUs currently reserved by s_res (0 = streams not created)
   int cu_masks_ok = 1;       // cleared when hipExtStreamCreateWithCUMask is refused: the single-stream schedules are used
-  int lookahead = -1;        // -1: by size; 0: single stream; 1: two-stream lookahead of round 1 (only with aggregate = 1); 2: reserved-CU schedule
-  // inverse overlapped with the factorization: the part that needs only the first h block rows runs on s_inv
-  int overlap_inverse = -1;  // -1 = by size (from N = 4096 with at least two outputs: -4 % at 4096, -6 % at 6144, -2.5 % at 8192; neutral below), 0 / 1 = off / on
   hipStream_t s_inv = nullptr;
   hipEvent_t ev_half = nullptr, ev_inv_early = nullptr;
   int early_inverse_started = 0;
@@ -110,11 +103,9 @@ struct bocf_ctx {
   long long sched_timeouts = 0;   // how often that happened (bocf_get_stat "sched_timeouts")
   int sched_retry = 0;       // the next factorization attempt is the redo of one that timed out: single-stream
   long long fits_done = 0;   // successful bocf_fit calls of this context
-  int last_schedule = 0;     // schedule of the last factorization: 0 single stream, 2 reserved CUs
+  int last_schedule = 0;     // schedule of the last factorization (CholSchedule): 0 launched, 2 reserved CUs, 3 one team launch, 4 team panel groups, 5 hybrid
   int sched_m = 0;           // > 0: choose the schedule as for this many outputs (the helper context of an output-sharded fit)
-  int force_sched_timeout = 0, force_cu_count = 0;   // test hooks (BOCF_PROBES builds only)
-  int lookahead_min_nb = 8;  // reserved-CU lookahead from this many 128-panels on
-  int aggregate = 0;         // panels per trailing update of the blocked Cholesky (0 = by size, 1 = classic right-looking)
+  int force_sched_timeout = 0;   // test hook (BOCF_PROBES builds only)
   int data_N = 0, data_d = 0, data_m = 0;   // shape of the X / Y resident on the device
   int fused_infer = 1;       // bocf_infer: one fused launch for N <= 128, d <= 16
   int reuse_data = 0;        // next bocf_fit calls: X, Y (and N, d, m) are those of the previous fit -- only the hyper-parameters change
@@ -170,9 +161,6 @@ struct bocf_ctx {
   bool profile = false;
   double test_diag_shift = 0.0;
   int prefetch1 = 0;
-  int merge_x3 = 1;          // the second product of an inverse merge in the three-buffer triangular kernel: 0 never, 1 from 4096 rows, 2 whenever possible
-  int potrf_scalar = 0;      // probes build: 11..14 = timing-only variants of the diagonal-block kernel
-  int trsm_wave = 1;         // row solves of the factorization through the wave-level single-tile kernel (0: the 128 x 128 GEMM kernel)
   int kstar_valu_probe = 0;  // timing-only experiment (gemm_f64.hip, VPROBE)
   int small_path = 1;        // GEMV-shaped path for <= 16 candidates
   int hyper_samples = 1;     // H: the m outputs are H groups (hyper-samples, group-major) of m / H model outputs

@@ -159,7 +159,7 @@ struct TeamArgs {
   double* E; double* ET; long strideE;              // inverted diagonal blocks
   int N, Np, nb;
   int* info;                                        // per output: LAPACK-style info of the diagonal blocks
-  int* F; int fstride;                              // per-output counters (chol_team_flag_words(nb) ints each), zeroed by the caller
+  int* F; int fstride;                              // per-output counters (chol_team_flag_words(nb) ints each, chol_plan.h), zeroed by the caller
   int* err;                                         // first wait that ran out of polls (0 = none)
   int T;                                            // workgroups per team (>= 2)
   int p0, p1;                                       // panels [p0, p1) of the factorization (the whole of it: 0, nb; do_inverse needs that)
@@ -169,8 +169,6 @@ struct TeamArgs {
   int stream;                                       // a workgroup of the team streams the critical tiles underneath the diagonal blocks (team_crit_stream)
   unsigned long long* tl;                           // probes build: per-workgroup task timeline (nullptr = off)
 };
-#define TEAM_MAX_NB 32
-int chol_team_flag_words(int nb);
 void launch_chol_team(const TeamArgs& a, int m, hipStream_t s);
 // whole inference (log-marginal + hyper-gradients) of a model with N <= 128, d <= 16 in one launch; yc has row stride 128
 #define BOCF_INFER_MAX_D 16

@@ -56,6 +56,9 @@ extern "C" int bocf_create(int device, bocf_ctx** out) {
     e = hipStreamCreateWithPriority(&c->stream2, hipStreamDefault, hi_prio);
   }
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_start, hipEventDisableTiming);
+  hipDeviceProp_t prop;
+  if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
+  if (e == hipSuccess) c->ncu = prop.multiProcessorCount;
   if (e != hipSuccess) {
     delete c;
     return fail("hipStreamCreate", hipGetErrorString(e));
@@ -148,21 +151,21 @@ static const OptDesc g_options[] = {
     {"fused_infer", 0, 1, 0, [](bocf_ctx* c, long long v) { c->fused_infer = v != 0; }, nullptr, "one fused launch per inference for N <= 128"},
     {"reuse_data", 0, 1, 1, [](bocf_ctx* c, long long v) { c->reuse_data = v != 0; }, nullptr, "next fits reuse the resident X / Y"},
     {"skip_mu_train", 0, 1, 1, [](bocf_ctx* c, long long v) { c->skip_mu_train = v != 0; }, nullptr, "do not refresh the mean at the training inputs"},
-    {"aggregate", 0, 8, 0, [](bocf_ctx* c, long long v) { c->aggregate = (int)v; }, nullptr, "panels per trailing update (0 = by size)"},
-    {"lookahead", -1, 2, 0, [](bocf_ctx* c, long long v) { c->lookahead = (int)v; }, opt_lookahead_ok,
+    {"aggregate", 0, 8, 0, [](bocf_ctx* c, long long v) { c->chol.aggregate = (int)v; }, nullptr, "panels per trailing update (0 = by size)"},
+    {"lookahead", -1, 2, 0, [](bocf_ctx* c, long long v) { c->chol.lookahead = (int)v; }, opt_lookahead_ok,
      "factorization schedule: -1 by size, 0 single stream, 2 reserved-CU chain"},
-    {"team_fit", -1, 1, 0, [](bocf_ctx* c, long long v) { c->team_fit = (int)v; }, nullptr, "factorization + inverse in one launch by resident workgroup teams (-1 = by size)"},
-    {"team_panels", 1, 32, 0, [](bocf_ctx* c, long long v) { c->team_panels = (int)v; }, nullptr, "team schedule above 8 panels: panels per team launch (one trailing update each)"},
-    {"team_hybrid", 0, 2, 0, [](bocf_ctx* c, long long v) { c->team_hybrid = (int)v; }, nullptr, "more than 24 panels: launched schedule for the first block rows, one team launch for the rest"},
-    {"team_tail_share", 1, 8, 0, [](bocf_ctx* c, long long v) { c->team_tail_share = (int)v; }, nullptr, "hybrid schedule: eighths of the compute units the tail's teams take"},
-    {"team_whole_max", 2, 32, 0, [](bocf_ctx* c, long long v) { c->team_whole_max = (int)v; }, nullptr, "panels up to which one team launch does the whole factorization and inverse"},
-    {"team_stream", 0, 1, 0, [](bocf_ctx* c, long long v) { c->team_stream = (int)v; }, nullptr, "teams: the critical tiles are formed underneath the diagonal blocks, 16 rows at a time"},
-    {"team_crit_load", 0, 4096, 0, [](bocf_ctx* c, long long v) { c->team_crit_load = (int)v; }, nullptr, "teams: critical-chain workgroups carry nothing else while the others get by with <= this many units each"},
-    {"lookahead_min_nb", 2, 1 << 20, 0, [](bocf_ctx* c, long long v) { c->lookahead_min_nb = (int)v; }, nullptr, "reserved-CU schedule from this many panels"},
-    {"merge_x3", 0, 2, 0, [](bocf_ctx* c, long long v) { c->merge_x3 = (int)v; }, nullptr, "second product of an inverse merge in the three-buffer kernel"},
+    {"team_fit", -1, 1, 0, [](bocf_ctx* c, long long v) { c->chol.team_fit = (int)v; }, nullptr, "factorization + inverse in one launch by resident workgroup teams (-1 = by size)"},
+    {"team_panels", 1, 32, 0, [](bocf_ctx* c, long long v) { c->chol.team_panels = (int)v; }, nullptr, "team schedule above 8 panels: panels per team launch (one trailing update each)"},
+    {"team_hybrid", 0, 2, 0, [](bocf_ctx* c, long long v) { c->chol.team_hybrid = (int)v; }, nullptr, "more than 24 panels: launched schedule for the first block rows, one team launch for the rest"},
+    {"team_tail_share", 1, 8, 0, [](bocf_ctx* c, long long v) { c->chol.team_tail_share = (int)v; }, nullptr, "hybrid schedule: eighths of the compute units the tail's teams take"},
+    {"team_whole_max", 2, 32, 0, [](bocf_ctx* c, long long v) { c->chol.team_whole_max = (int)v; }, nullptr, "panels up to which one team launch does the whole factorization and inverse"},
+    {"team_stream", 0, 1, 0, [](bocf_ctx* c, long long v) { c->chol.team_stream = (int)v; }, nullptr, "teams: the critical tiles are formed underneath the diagonal blocks, 16 rows at a time"},
+    {"team_crit_load", 0, 4096, 0, [](bocf_ctx* c, long long v) { c->chol.team_crit_load = (int)v; }, nullptr, "teams: critical-chain workgroups carry nothing else while the others get by with <= this many units each"},
+    {"lookahead_min_nb", 2, 1 << 20, 0, [](bocf_ctx* c, long long v) { c->chol.lookahead_min_nb = (int)v; }, nullptr, "reserved-CU schedule from this many panels"},
+    {"merge_x3", 0, 2, 0, [](bocf_ctx* c, long long v) { c->chol.merge_x3 = (int)v; }, nullptr, "second product of an inverse merge in the three-buffer kernel"},
     {"shard_fit", 0, 1, 0, [](bocf_ctx* c, long long v) { c->shard_fit = v != 0; }, nullptr, "output-sharded fit over the communicator"},
-    {"trsm_wave", 0, 1, 0, [](bocf_ctx* c, long long v) { c->trsm_wave = v != 0; }, nullptr, "row solves through the wave-level single-tile kernel"},
-    {"overlap_inverse", -1, 1, 0, [](bocf_ctx* c, long long v) { c->overlap_inverse = (int)v; }, nullptr, "early part of the inverse underneath the factorization (-1 = by size)"},
+    {"trsm_wave", 0, 1, 0, [](bocf_ctx* c, long long v) { c->chol.trsm_wave = v != 0; }, nullptr, "row solves through the wave-level single-tile kernel"},
+    {"overlap_inverse", -1, 1, 0, [](bocf_ctx* c, long long v) { c->chol.overlap_inverse = (int)v; }, nullptr, "early part of the inverse underneath the factorization (-1 = by size)"},
     {"overlap", 0, 1, 0, [](bocf_ctx* c, long long v) { c->overlap = v != 0; }, nullptr, "K* build on a second stream"},
     {"small_path", 0, 1, 0, [](bocf_ctx* c, long long v) { c->small_path = v != 0; }, nullptr, "GEMV-shaped path for <= 16 candidates"},
     {"prefetch1", 0, 1, 0, [](bocf_ctx* c, long long v) { c->prefetch1 = v != 0; }, nullptr, "one-tile-deep staging in the 128-row variance kernel"},
@@ -176,13 +179,13 @@ static const OptDesc g_options[] = {
     {"acq_hyper_samples", 0, 64, 1, [](bocf_ctx* c, long long v) { c->acq_hyper_samples = (int)v; }, nullptr, "hyper-samples the acquisitions average over (0 = all)"},
     {"best_group", -1, 63, 1, [](bocf_ctx* c, long long v) { c->best_group = (int)v; }, nullptr, "whose best-so-far every hyper-sample uses (-1 = its own)"},
 #ifdef BOCF_PROBES
-    {"potrf_scalar", 0, 14, 2, [](bocf_ctx* c, long long v) { c->potrf_scalar = (int)v; }, opt_potrf_ok, "TIMING-ONLY variants of the diagonal-block kernel: 11..14 (wrong results)"},
+    {"potrf_scalar", 0, 14, 2, [](bocf_ctx* c, long long v) { c->chol.potrf_scalar = (int)v; }, opt_potrf_ok, "TIMING-ONLY variants of the diagonal-block kernel: 11..14 (wrong results)"},
     {"shard_fit_simulate", 0, 64, 2, [](bocf_ctx* c, long long v) { c->shard_fit_simulate = (int)v; }, nullptr, "TEST HOOK: one process plays all G ranks of a sharded fit"},
     {"kstar_valu_probe", 0, 4, 2, [](bocf_ctx* c, long long v) { c->kstar_valu_probe = (int)v; }, nullptr, "TIMING-ONLY variants of the two-buffer 256-row variance kernel (wrong results)"},
     {"test_diag_shift_1e12", -1000000000000000LL, 1000000000000000LL, 2, [](bocf_ctx* c, long long v) { c->test_diag_shift = (double)v * 1e-12; }, nullptr,
      "TEST HOOK: Ky diagonal -= value * 1e-12 (forces the jitter ladder)"},
     {"force_sched_timeout", 0, 1, 2, [](bocf_ctx* c, long long v) { c->force_sched_timeout = (int)v; }, nullptr, "TEST HOOK: the next gated schedule reports a dependency time-out"},
-    {"force_cu_count", 0, 4096, 2, [](bocf_ctx* c, long long v) { c->force_cu_count = (int)v; }, nullptr, "TEST HOOK: pretend the device has this many compute units (schedule selection)"},
+    {"force_cu_count", 0, 4096, 2, [](bocf_ctx* c, long long v) { c->chol.force_cu_count = (int)v; }, nullptr, "TEST HOOK: pretend the device has this many compute units (schedule selection)"},
 #endif
 };
 static const int g_noptions = (int)(sizeof(g_options) / sizeof(g_options[0]));

@@ -47,7 +47,7 @@ static GemmArgs trsm_args(bocf_ctx* c, int p, int W) {
 // option says otherwise
 static void launch_trsm(bocf_ctx* c, int p, int W, hipStream_t st) {
   if (W <= 0) return;
-  if (c->trsm_wave) {
+  if (c->chol.trsm_wave) {
     const int Np = c->Np;
     const long strideS = (long)Np * Np, strideE = (long)(Np / BOCF_TILE) * BOCF_TILE * BOCF_TILE;
     double* panel = wS(c) + (long)p * BOCF_TILE * Np + (long)(p + 1) * BOCF_TILE;
@@ -73,11 +73,10 @@ static GemmArgs syrk_args(bocf_ctx* c, int p, int first, int rows, int W) {
   return t;
 }
 
-// (Re)create the three masked streams for `want` reserved compute units.  Mask bit i selects CU (i / 8) of XCD (i % 8) on
+// (Re)create the three masked streams for `want` of `ncu` compute units reserved.  Mask bit i selects CU (i / 8) of XCD (i % 8) on
 // MI355X (tools/cumask_probe.hip), so 8 k reserved bits take k CUs from every XCD.
-// Returns 0 = streams ready; 1 = the schedule does not apply (too few CUs for `want`, or the runtime refuses CU masks -- then
-// cu_masks_ok is cleared) and the caller must fall through to a single-stream schedule; -1 = a HIP error (recorded).
-static int ensure_reserved_streams(bocf_ctx* c, int want) {
+// Returns 0 = streams ready; 1 = the runtime refuses CU masks (cu_masks_ok is cleared); -1 = a HIP error (recorded).
+static int ensure_reserved_streams(bocf_ctx* c, int want, int ncu) {
   if (c->res_cus == want && c->s_res) return 0;
   for (hipStream_t* st : {&c->s_res, &c->s_hi, &c->s_bulk})
     if (*st) {
@@ -85,10 +84,6 @@ static int ensure_reserved_streams(bocf_ctx* c, int want) {
       *st = nullptr;
     }
   c->res_cus = 0;
-  hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, c->device));
-  const int ncu = c->force_cu_count > 0 ? c->force_cu_count : prop.multiProcessorCount;
-  if (want >= ncu / 2) return 1;                         // not applicable on this device / for this many outputs: no error, the caller falls through
   const int words = (ncu + 31) / 32;
   std::vector<uint32_t> res(words, 0u), rest(words, 0u);
   for (int i = 0; i < ncu; ++i) (i < want ? res : rest)[i / 32] |= 1u << (i % 32);
@@ -112,7 +107,6 @@ static int ensure_reserved_streams(bocf_ctx* c, int want) {
 }
 
 static void trtri_early(bocf_ctx* c, int h, hipStream_t st);
-static int trtri_split(int nb);
 enum { MERGE_FIRST = 1, MERGE_SECOND = 2 };
 static void merge_level(bocf_ctx* c, int lo, int w, int w2, int count, int which, hipStream_t st);
 
@@ -137,7 +131,7 @@ static void merge_level(bocf_ctx* c, int lo, int w, int w2, int count, int which
 // (bulkA(p-1) follows every older bulk on its in-order stream, so BA(p-1) stands for all of them.)  The chain per panel is
 // potrf + two single-tile products + three kernel boundaries on CUs nobody else may use; a trailing update has two chain
 // steps to finish before anything waits for it.
-static int run_cholesky_reserved(bocf_ctx* c) {
+static int run_cholesky_reserved(bocf_ctx* c, const CholPlan& plan) {
   const int Np = c->Np, m = c->m, nb = Np / BOCF_TILE;
   const long strideS = (long)Np * Np, strideE = (long)nb * BOCF_TILE * BOCF_TILE;
   double* S = wS(c);
@@ -147,17 +141,14 @@ static int run_cholesky_reserved(bocf_ctx* c) {
     c->ev_chol.push_back(ev);
   }
   const auto t_host0 = std::chrono::steady_clock::now();
-  // counters: 5 per panel + the timeout word, in a block of their own (multiple of 16 bytes), zeroed before every schedule
-  const size_t nflags = (size_t)((5 * nb + 1 + 3) / 4) * 4;
-  if (c->chol_flags.ensure(sizeof(int) * nflags)) return -1;
+  // counters: 5 per panel + the timeout word (plan.flag_ints, zeroed by run_cholesky_impl)
   int* F = c->chol_flags.as<int>();
-  HIPCHK(hipMemsetAsync(F, 0, sizeof(int) * nflags, c->stream));
   auto fP = [&](int p) { return F + 5 * p; };
   auto fT1 = [&](int p) { return F + 5 * p + 1; };
   auto fT2 = [&](int p) { return F + 5 * p + 2; };
   auto fR = [&](int p) { return F + 5 * p + 3; };
   auto fBA = [&](int p) { return F + 5 * p + 4; };
-  int* ferr = F + 5 * nb;
+  int* ferr = F + plan.err_off;
   hipEvent_t ev0 = c->ev_chol[0], evE1 = c->ev_chol[1], evE2 = c->ev_chol[2], evE3 = c->ev_chol[3];
   HIPCHK(hipEventRecord(ev0, c->stream));
   for (hipStream_t st : {c->s_res, c->s_hi, c->s_bulk}) HIPCHK(hipStreamWaitEvent(st, ev0, 0));
@@ -184,15 +175,12 @@ static int run_cholesky_reserved(bocf_ctx* c) {
                    fR(p));                                                                                                           // S2(p)
     // ---- the part of the inverse that needs only block rows [0, h) of U starts as soon as row h-1 is solved, on its own stream
     //      (complement CUs): from here on the chain sets the pace and the chip is mostly idle
-    {
-      const bool want = c->overlap_inverse > 0 || (c->overlap_inverse < 0 && nb >= 16 && (c->sched_m > 0 ? c->sched_m : m) >= 2);
-      if (want && c->s_inv && nb >= 8 && p == trtri_split(nb) - 1) {
-        HIPCHK(hipStreamWaitEvent(c->s_inv, ev0, 0));
-        launch_gate(fT2(p), 4 * nrest * m, fT1(p), 4 * m, ferr, c->s_inv);
-        trtri_early(c, trtri_split(nb), c->s_inv);
-        HIPCHK(hipEventRecord(c->ev_inv_early, c->s_inv));
-        c->early_inverse_started = 1;
-      }
+    if (p == plan.inv_after) {
+      HIPCHK(hipStreamWaitEvent(c->s_inv, ev0, 0));
+      launch_gate(fT2(p), 4 * nrest * m, fT1(p), 4 * m, ferr, c->s_inv);
+      trtri_early(c, plan.h, c->s_inv);
+      HIPCHK(hipEventRecord(c->ev_inv_early, c->s_inv));
+      c->early_inverse_started = 1;
     }
     // ---- trailing update below block row p+1
     launch_gate(fT2(p), 4 * nrest * m, nullptr, 0, ferr, c->s_bulk);
@@ -204,8 +192,6 @@ static int run_cholesky_reserved(bocf_ctx* c) {
   HIPCHK(hipEventRecord(evE2, c->s_hi));
   HIPCHK(hipEventRecord(evE3, c->s_bulk));
   for (hipEvent_t ev : {evE1, evE2, evE3}) HIPCHK(hipStreamWaitEvent(c->stream, ev, 0));
-  c->chol_flags_used = 1;
-  c->chol_err_off = 5 * nb;
 #ifdef BOCF_PROBES
   if (getenv("BOCF_DBG")) {
     const auto t1 = std::chrono::steady_clock::now();
@@ -217,24 +203,23 @@ static int run_cholesky_reserved(bocf_ctx* c) {
   return 0;
 }
 
-// Called by the single-stream Cholesky schedules right after the row solve of panel p: once block rows [0, h) of U are final
-// the part of the inverse that needs nothing else starts on the second stream, underneath the rest of the factorization
-// (whose second half is a chain of short launches that leaves most of the chip idle).
-static int maybe_start_early_inverse(bocf_ctx* c, int p) {
-  const int nb = c->Np / BOCF_TILE;
-  // (by size: from 24 panels -- N = 3072: 3.64 -> 3.57 ms, N = 3584: 4.84 -> 4.52; a tie below)
-  const bool want = c->overlap_inverse > 0 || (c->overlap_inverse < 0 && nb >= 24 && (c->sched_m > 0 ? c->sched_m : c->m) >= 2);
-  if (!want || nb < 8 || !c->s_inv) return 0;
-  const int h = trtri_split(nb);
-  if (!c->early_inverse_started && p == h - 1) {
-    HIPCHK(hipEventRecord(c->ev_half, c->stream));
-    HIPCHK(hipStreamWaitEvent(c->s_inv, c->ev_half, 0));
-    trtri_early(c, h, c->s_inv);
-    HIPCHK(hipEventRecord(c->ev_inv_early, c->s_inv));
-    c->early_inverse_started = 1;
-    // (a second stage -- the merges inside block rows [h, 3h/2) started when row 3h/2 - 1 is solved -- was measured in round 3: visible
-    //  inverse 1.22 -> 1.21 ms, Cholesky 4.62 -> 4.69 ms at config 3: neutral, not kept)
-  }
+// The part of the inverse that needs only block rows [0, h) of U starts on the second stream once they are final, underneath the rest of
+// the factorization (whose second half is a chain of short launches that leaves most of the chip idle).
+static int start_early_inverse(bocf_ctx* c, int h) {
+  HIPCHK(hipEventRecord(c->ev_half, c->stream));
+  HIPCHK(hipStreamWaitEvent(c->s_inv, c->ev_half, 0));
+  trtri_early(c, h, c->s_inv);
+  HIPCHK(hipEventRecord(c->ev_inv_early, c->s_inv));
+  return 0;
+}
+
+// Called by the single-stream Cholesky schedules right after the row solve of panel p.
+static int maybe_start_early_inverse(bocf_ctx* c, const CholPlan& plan, int p) {
+  if (p != plan.inv_after) return 0;
+  if (start_early_inverse(c, plan.h)) return -1;
+  c->early_inverse_started = 1;
+  // (a second stage -- the merges inside block rows [h, 3h/2) started when row 3h/2 - 1 is solved -- was measured in round 3: visible
+  //  inverse 1.22 -> 1.21 ms, Cholesky 4.62 -> 4.69 ms at config 3: neutral, not kept)
   return 0;
 }
 
@@ -280,7 +265,7 @@ static void chol_group_step(bocf_ctx* c, int p0, int G, hipStream_t st) {
       double* row = S + (long)p * BOCF_TILE * Np + (long)p * BOCF_TILE;
       t.Cin = row; t.Cout = row; t.ldc = Np; t.strideC = strideS;
       t.M = BOCF_TILE; t.Ncols = W + BOCF_TILE; t.K = q * BOCF_TILE; t.kb = q * BOCF_TILE; t.alpha = -1.0; t.beta = 1.0;
-      if (c->trsm_wave)   // one block row, short K: the wave-level kernel (latency-bound either way, half the time)
+      if (c->chol.trsm_wave)   // one block row, short K: the wave-level kernel (latency-bound either way, half the time)
         launch_tile128(rows, Np, strideS, rows, Np, strideS, row, Np, strideS, -1.0, 1.0, m, st, (W + BOCF_TILE) / BOCF_TILE, q * BOCF_TILE);
       else
         launch_gemm_f64(t, m, 0, st);
@@ -293,39 +278,20 @@ static void chol_group_step(bocf_ctx* c, int p0, int G, hipStream_t st) {
 
 
 // Factorization AND inverse in one launch by resident workgroup teams (chol_team.hip), for models with few panels: the launched
-// schedules below are then a chain of ~10 short dependent launches per panel with the chip idle underneath.  Returns 1 when the
-// schedule does not apply (the caller falls through), 0 when it was enqueued, -1 on a HIP error.
-static int run_cholesky_team(bocf_ctx* c, int G, int pfirst = 0, int pend = -1) {
-  const int Np = c->Np, m = c->m, nb = Np / BOCF_TILE;
-  if (nb < 2 || (G <= 0 && nb - pfirst > TEAM_MAX_NB)) return 1;
-  if (c->ncu <= 0) {
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, c->device));
-    c->ncu = prop.multiProcessorCount;
-  }
-  const int ncu = c->force_cu_count > 0 ? c->force_cu_count : c->ncu;
-  if (ncu < 4) return 1;
-  if (pend < 0) pend = nb;
-  const bool whole = (G <= 0 || G >= nb) && pend == nb;    // one launch: factorization and inverse (of the panels from pfirst on)
+// schedules below are then a chain of ~10 short dependent launches per panel with the chip idle underneath.  Panels [pfirst, pend) in
+// teams of T workgroups: G = 0 ONE launch (factorization and inverse of the block from pfirst on, pend = nb), else launches of G panels,
+// each followed by a trailing update.  Returns 0, or -1 on a HIP error.
+static int run_cholesky_team(bocf_ctx* c, const CholPlan& plan, int pfirst, int pend, int G, int T) {
+  const int Np = c->Np, m = c->m, nb = Np / BOCF_TILE, mb = plan.mb;
+  const bool whole = G <= 0;
   const int g_max = whole ? nb - pfirst : G;
-  // every workgroup of a launch must be resident at once: one 12-wave workgroup per compute unit at most
-  const bool kinv = whole && pfirst == 0 && c->want_kinv;
-  const int nt = nb - pfirst;
-  const int units = whole ? 2 * (nt * (nt + 1) / 2 - 1) + nt * (nt - 1) + (kinv ? nb * (nb + 1) : 0) : 2 * (g_max * nb - 1);
-  int mb = m < ncu / 2 ? m : ncu / 2;                      // outputs per launch
-  int T = ncu / mb;
-  if (pfirst > 0 && c->team_tail_share > 0) T = T * c->team_tail_share / 8;     // (hybrid: leave compute units to the inverse running underneath)
-  if (T > 2 + units) T = 2 + units;                        // (the diagonal workgroup, the streaming workgroup, one per unit)
-  if (T < 2) return 1;
+  const bool kinv = whole && plan.kinv;
   const long strideS = (long)Np * Np, strideE = (long)nb * BOCF_TILE * BOCF_TILE;
-  const int words = chol_team_flag_words(nb);
-  const size_t nflags = (size_t)m * words + 4;
-  if (c->chol_flags.ensure(sizeof(int) * nflags)) return -1;
+  const int words = chol_team_flag_words(nb);            // (the counters of output j, then the time-out word at plan.err_off)
   int* F = c->chol_flags.as<int>();
-  if (!c->flags_device_zeroed) HIPCHK(hipMemsetAsync(F, 0, sizeof(int) * nflags, c->stream));
 #ifdef BOCF_PROBES
   const char* tl_path = getenv("BOCF_TEAM_TL");            // probes build: per-task stamps of every workgroup of the LAST launch (tools/team_timeline.py)
-  const size_t tl_words = (size_t)ncu * 512 * 4;
+  const size_t tl_words = (size_t)plan.ncu * 512 * 4;
   if (tl_path && !c->team_tl) HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->team_tl), sizeof(unsigned long long) * tl_words));
 #endif
   for (int p0 = pfirst; p0 < pend; p0 += g_max) {
@@ -343,11 +309,11 @@ static int run_cholesky_team(bocf_ctx* c, int G, int pfirst = 0, int pend = -1) 
       a.N = c->N; a.Np = Np; a.nb = nb;
       a.info = winfo(c) + j0;
       a.F = F + (size_t)j0 * words; a.fstride = words;
-      a.err = F + (size_t)m * words;
+      a.err = F + plan.err_off;
       a.T = T; a.p0 = p0; a.p1 = p0 + g; a.do_inverse = whole ? 1 : 0; a.tl = nullptr;
       a.KI = wT(c) + (long)j0 * strideS; a.do_kinv = kinv ? 1 : 0;
       // (streaming the critical tiles pays while the chain of diagonal blocks sets the pace: measured m = 4, 16 panels 1.11 -> 0.99 ms, 20: a tie, 24: 2.52 -> 2.63)
-      a.crit_load = c->team_crit_load; a.stream = c->team_stream && g <= 20 ? 1 : 0;
+      a.crit_load = c->chol.team_crit_load; a.stream = c->chol.team_stream && g <= 20 ? 1 : 0;
 #ifdef BOCF_PROBES
       a.tl = tl_this ? c->team_tl : nullptr;
 #endif
@@ -355,8 +321,8 @@ static int run_cholesky_team(bocf_ctx* c, int G, int pfirst = 0, int pend = -1) 
     }
     if (!whole) {
       launch_trailing_update(c, p0, g, c->stream);
-      for (int p = p0; p < p0 + g && pend == nb; ++p)      // (a caller that stops at pend starts the inverse itself)
-        if (maybe_start_early_inverse(c, p)) return -1;
+      for (int p = p0; p < p0 + g && pend == nb; ++p)      // (the hybrid, which stops at pend, starts the inverse itself)
+        if (maybe_start_early_inverse(c, plan, p)) return -1;
     }
   }
 #ifdef BOCF_PROBES
@@ -366,7 +332,7 @@ static int run_cholesky_team(bocf_ctx* c, int G, int pfirst = 0, int pend = -1) 
     HIPCHK(hipStreamSynchronize(c->stream));
     if (FILE* f = fopen(tl_path, "w")) {
       fprintf(f, "# T %d nb %d m %d\n", T, nb, m);
-      for (size_t b = 0; b < (size_t)ncu; ++b)
+      for (size_t b = 0; b < (size_t)plan.ncu; ++b)
         for (size_t k = 0; k < 512; ++k) {
           const unsigned long long* r = h.data() + (b * 512 + k) * 4;
           if (r[0]) fprintf(f, "%zu %llu %llu %llu %llu\n", b, r[0], r[1], r[2], r[3]);
@@ -375,14 +341,11 @@ static int run_cholesky_team(bocf_ctx* c, int G, int pfirst = 0, int pend = -1) 
     }
   }
 #endif
-  c->chol_flags_used = 1;
-  c->chol_err_off = m * words;
-  if (whole) {
+  if (whole && pfirst == 0) {
     // (the teams write R^T (lower) and, transposed, R (upper): the strictly lower half of R / upper half of R^T is the zero half no fit ever writes)
-    c->inverse_done = pfirst == 0 ? 1 : 0;
+    c->inverse_done = 1;
     c->kinv_done = kinv ? 1 : 0;
   }
-  c->last_schedule = whole ? (pfirst == 0 ? 3 : 5) : 4;
   return 0;
 }
 
@@ -392,126 +355,96 @@ static int run_cholesky_team(bocf_ctx* c, int G, int pfirst = 0, int pend = -1) 
 // nb - h <= 24 panels, where the chain of diagonal blocks is what matters and the teams win).  h = the inverse's own split (largest power of
 // two below nb): the inverse of the first h block rows and the first product of the top-level merge run on the second stream underneath,
 // as in the launched schedule; after the team launch only R22 = (R22^T)^T and the merge's second product  R12 = -(R11 U12) R22  are left.
-static int run_cholesky_hybrid(bocf_ctx* c, int G) {
-  const int Np = c->Np, nb = Np / BOCF_TILE;
-  const int h = trtri_split(nb);                           // (the split one level lower -- 8 + 24 panels at N = 4096 -- was measured: 6.5 ms against 4.9)
-  if (nb - h > 24 || nb - h < 2 || !c->s_inv) return 1;
-  if (c->ncu <= 0) {
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, c->device));
-    c->ncu = prop.multiProcessorCount;
-  }
-  if ((c->force_cu_count > 0 ? c->force_cu_count : c->ncu) < 4) return 1;
-  if (c->team_hybrid == 2) {                               // (A/B: the first block rows by team launches of team_panels panels + trailing updates)
-    const int rs0 = run_cholesky_team(c, c->team_panels > 0 ? c->team_panels : 4, 0, h);
-    if (rs0 != 0) return rs0 < 0 ? -1 : 2;
+// The two parts share one zeroing of the counter block: a team launch over panels [p0, p1) touches only the counters of panels and block
+// rows >= p0 -- P, D, ST, RD of its own panels, TR / IR rows from p0 on -- and reads the next panel's P only while that is still unwritten, so
+// the first part's counters (rows < h) and the tail's (rows >= h) are disjoint, as those of the first part's successive launches are.  The
+// time-out word is shared: one that fires in the first part reaches bocf_fit.
+static int run_cholesky_hybrid(bocf_ctx* c, const CholPlan& plan) {
+  const int nb = c->Np / BOCF_TILE, h = plan.h;
+  if (plan.panels > 0) {                                   // (A/B: the first block rows by team launches of team_panels panels + trailing updates)
+    if (run_cholesky_team(c, plan, 0, h, plan.panels, plan.T)) return -1;
   } else {
-    for (int p0 = 0; p0 < h; p0 += G) chol_group_step(c, p0, h - p0 < G ? h - p0 : G, c->stream);
+    for (int p0 = 0; p0 < h; p0 += plan.G) chol_group_step(c, p0, h - p0 < plan.G ? h - p0 : plan.G, c->stream);
   }
   // the first h block rows of U are final: their inverse, and the first product of the top-level merge, underneath the team launch
-  HIPCHK(hipEventRecord(c->ev_half, c->stream));
-  HIPCHK(hipStreamWaitEvent(c->s_inv, c->ev_half, 0));
-  trtri_early(c, h, c->s_inv);
-  HIPCHK(hipEventRecord(c->ev_inv_early, c->s_inv));
-  const int rs = run_cholesky_team(c, 0, h);
-  if (rs != 0) return rs < 0 ? -1 : 2;                     // (2: the team launch does not apply after all -- the caller finishes with the launched schedule)
+  if (start_early_inverse(c, h)) return -1;
+  if (run_cholesky_team(c, plan, h, nb, 0, plan.T_tail)) return -1;
   HIPCHK(hipStreamWaitEvent(c->stream, c->ev_inv_early, 0));
   merge_level(c, 0, h, nb - h, 1, MERGE_SECOND, c->stream);
   c->inverse_done = 1;
-  c->last_schedule = 5;
   return 0;
 }
 
-static int run_cholesky_impl(bocf_ctx* c);
-int bocf_run_cholesky(bocf_ctx* c) {
+// The launched schedule: everything on the context's stream, G panels per trailing update.
+static int run_cholesky_launched(bocf_ctx* c, const CholPlan& plan) {
+  const int nb = c->Np / BOCF_TILE;
+  for (int p0 = 0; p0 < nb; p0 += plan.G) {
+    chol_group_step(c, p0, plan.G, c->stream);
+    for (int p = p0; p < p0 + plan.G && p < nb; ++p)
+      if (maybe_start_early_inverse(c, plan, p)) return -1;
+  }
+  return 0;
+}
+
+// The schedule of the next factorization of c (chol_plan.h) and what it needs: the reserved-CU streams, the counter block.  The one
+// refusal the runtime may still make -- CU masks (hipExtStreamCreateWithCUMask) -- comes before anything is enqueued and is planned round.
+int bocf_plan_cholesky(bocf_ctx* c, CholPlan* out) {
+  CholPlanInput in;
+  in.nb = c->Np / BOCF_TILE; in.m = c->m; in.sched_m = c->sched_m; in.ncu = c->ncu;
+  in.inv_stream = c->s_inv != nullptr; in.cu_masks_ok = c->cu_masks_ok; in.gated_off = c->gated_off; in.sched_retry = c->sched_retry;
+  in.refit = c->fits_done > 0; in.want_kinv = c->want_kinv;
+  c->sched_retry = 0;
+  CholPlan plan = plan_cholesky(in, c->chol);
+  if (plan.schedule == CHOL_RESERVED) {
+    const int rs = ensure_reserved_streams(c, plan.reserved_cus, plan.ncu);
+    if (rs < 0) return -1;
+    if (rs > 0) {                                          // (cu_masks_ok is cleared for the context's later fits too)
+      in.cu_masks_ok = false;
+      plan = plan_cholesky(in, c->chol);
+    }
+  }
+  if (plan.flag_ints > 0 && c->chol_flags.ensure(sizeof(int) * plan.flag_ints)) return -1;
+  *out = plan;
+  return 0;
+}
+
+static int run_cholesky_impl(bocf_ctx* c, const CholPlan& plan) {
+  c->early_inverse_started = 0;
+  c->inverse_done = 0;
+  c->kinv_done = 0;
+  c->last_schedule = plan.schedule;
+  c->chol_flags_used = plan.flag_ints > 0 ? 1 : 0;
+  c->chol_err_off = plan.err_off;
+  set_potrf_scalar(c->chol.potrf_scalar);                // (probes build: timing-only variants of the diagonal-block kernel)
+  // the counters and the time-out word, zeroed ONCE per factorization (for the team schedule of a stream-resident HMC chain its kernels do it)
+  if (plan.flag_ints > 0 && !c->flags_device_zeroed) HIPCHK(hipMemsetAsync(c->chol_flags.p, 0, sizeof(int) * plan.flag_ints, c->stream));
+  const int nb = c->Np / BOCF_TILE;
+  switch (plan.schedule) {
+    case CHOL_TEAM_WHOLE: return run_cholesky_team(c, plan, 0, nb, 0, plan.T);
+    case CHOL_TEAM_GROUPS: return run_cholesky_team(c, plan, 0, nb, plan.panels, plan.T);
+    case CHOL_RESERVED: return run_cholesky_reserved(c, plan);
+    case CHOL_HYBRID: return run_cholesky_hybrid(c, plan);
+    case CHOL_LAUNCHED: break;
+  }
+  return run_cholesky_launched(c, plan);
+}
+
+int bocf_run_cholesky(bocf_ctx* c, const CholPlan* chain_plan) {
+  CholPlan plan;
+  if (chain_plan) plan = *chain_plan;
+  else if (bocf_plan_cholesky(c, &plan)) return -1;
 #ifdef BOCF_PROBES
   const char* tl = getenv("BOCF_DBG_TL");                // plain-run timeline of the chain kernels (tools/dbg_timeline.py)
   if (tl) {
     HIPCHK(hipStreamSynchronize(c->stream));
     dbg_tl_start();
   }
-  const int rc = run_cholesky_impl(c);
+  const int rc = run_cholesky_impl(c, plan);
   if (tl && rc == 0) dbg_tl_dump(tl);
   return rc;
 #else
-  return run_cholesky_impl(c);
+  return run_cholesky_impl(c, plan);
 #endif
-}
-static int run_cholesky_impl(bocf_ctx* c) {
-  const int Np = c->Np, m = c->m, nb = Np / BOCF_TILE;
-  const long strideS = (long)Np * Np, strideE = (long)nb * BOCF_TILE * BOCF_TILE;
-  double* S = wS(c);
-  c->early_inverse_started = 0;
-  c->inverse_done = 0;
-  c->kinv_done = 0;
-  set_potrf_scalar(c->potrf_scalar);                     // (probes build: timing-only variants of the diagonal-block kernel)
-  // schedule: option "lookahead" = 2 (default by size: nb >= 8, at most 64 factorizations) -> reserved-CU lookahead
-  // reserved-CU schedule with device-side dependencies: where the CHAIN of diagonal blocks sets the pace (few panels, or few
-  // outputs per panel) it wins -- N = 2048 m = 4: 2.83 -> 2.52 ms, N = 3072: 5.4 -> 4.6, N = 4096 m = 1: 5.83 -> 4.57 -- where the
-  // trailing updates do (N >= 6144 with m = 4: 17.7 vs 18.9 ms) the aggregated single-stream schedule below does.
-  // "lookahead" = 2 forces it, -1 (default) chooses by size, 0 never uses it.  (Removed in round 3, all measured slower in plain runs and
-  // kept until then for A/B: 1 = next panel's diagonal block + row solve on a second stream with stream events, 3 / 4 = panel pairs with
-  // lookahead on two / three masked streams; their numbers are in DESIGN.md 10 and profiles/r02.)
-  const int m_sched = c->sched_m > 0 ? c->sched_m : m;     // (a shard helper chooses as the replicated fit of ALL outputs would)
-  // re-measured at the end of round 3 (tools/fit_schedule_sweep.sh, profiles/r03/fit_schedule_sweep.txt; the diagonal-block kernel, the row
-  // products and the inverse all got faster since the rule was set, the cross-stream hand-overs did not): with two or more outputs the
-  // single-stream schedule now wins from N = 2048 up by 10-50 % (N = 3072, m = 4: 3.62 against 5.38 ms; N = 4096, m = 2: 4.26 against 6.27);
-  // the reserved-CU chain keeps ONE output (7-9 % at every size) and two outputs up to 12 panels (4 %)
-  const bool reserved_auto = c->lookahead < 0 && nb >= 8 && ((m_sched == 1 && nb <= 32) || (m_sched == 2 && nb <= 12));
-  // The gated (multi-stream) schedules are not used: after dependency time-outs (gated_off), for the redo of an attempt that timed out
-  // (sched_retry), and for the FIRST factorization of a context -- it pays the one-time costs (code-object loads, allocations, stream
-  // creation) that would otherwise sit between the launch of a polling kernel and the launch of the kernel it waits for.
-  const bool gated_ok = c->cu_masks_ok && !c->gated_off && !c->sched_retry && c->fits_done > 0;
-  // resident teams: few panels, not after dependency time-outs, not for the redo of an attempt that timed out
-  const bool team_ok = !c->gated_off && !c->sched_retry && (c->team_fit > 0 || (c->lookahead < 0 && c->aggregate <= 0));
-  // by size (m = 4, Cholesky + inverse in ms, launched / teams): 9 panels 1.05 / 0.56, 12: 1.34 / 0.75, 16: 1.76 / 1.10, 20: 2.56 / 1.8, 24: 3.32 / 2.51,
-  // 32: 5.23 / 5.84 -- from there the K = 128 .. 512 unit products of the teams (~0.2 TFLOP/s per CU) lose to the launched GEMMs
-  const int whole_max = c->team_whole_max;                 // up to here ONE team launch does everything; beyond, the hybrid schedule
-  const bool team_auto = c->team_fit < 0 && nb >= 2 && nb <= 24;
-  c->sched_retry = 0;
-  if ((c->team_fit > 0 || team_auto) && team_ok && (nb <= whole_max || !c->team_hybrid)) {
-    const int rs = run_cholesky_team(c, nb <= 24 ? 0 : c->team_panels);
-    if (rs <= 0) return rs;
-  }
-  if ((c->lookahead == 2 || reserved_auto) && gated_ok && nb >= (c->lookahead == 2 ? 2 : c->lookahead_min_nb) && m <= 64 && c->aggregate <= 0) {
-    const int rs = ensure_reserved_streams(c, ((m + 7) / 8) * 8);
-    if (rs < 0) return -1;
-    if (rs == 0) {
-      c->last_schedule = 2;
-      return run_cholesky_reserved(c);
-    }
-  }
-  c->last_schedule = 0;
-  // measured (m = 4): N=2048 4 % slower, N=4096 3 % faster, N=8192 5 % faster -- the diagonal-block workgroup runs 1.6-2x
-  // slower when it shares its CU with trailing-update waves, which eats most of what the overlap hides
-  // measured (m = 4, ms): N=2048 3.82 / 3.90 / 4.13 for G = 1 / 2 / 4; N=4096 11.45 / 11.17 / 11.45; N=8192 56.3 / 50.4 / 48.7
-  // re-measured with the MFMA diagonal-block kernel and the row-staged epilogue (profiles/r02/fit_schedule_sweep.txt):
-  // G = 1 is best up to N = 3072, 2 at 4096, 3 at 6144 and 8192
-  // (G = 3 at N = 4096 is 0.15 ms faster than G = 2 with the factor-wave diagonal kernel, but at cond(Ky) ~ 4e9 the other summation order moves
-  // two of config 3's small acquisition values by 2.5e-5 relative, past the 1e-5 gate of test_config3_full_size: not taken)
-  // re-measured at the end of round 3 (m = 4, Cholesky ms for G = 1 / 2 / 3): N = 2048 1.27 / 1.19 / 1.20, 2560 1.77 / 1.69 / 1.65, 3072 3.05 / 2.92 / 3.06,
-  // 3584 3.65 / 3.49 / 3.66, 4096 4.73 / 4.30 / 4.16, 5120 9.71 / 9.30 / 9.27, 6144 13.6 / 12.8 / 12.4: pairs from 16 panels, triples from 32 (with alpha
-  // refined every G sits a decade inside the truth gate of tests/test_gpu_round3.py, so the choice is a matter of speed only)
-  const int G_auto = nb >= 32 ? 3 : (nb >= 16 ? 2 : 1);
-  const int G_use = c->aggregate > 0 ? c->aggregate : G_auto;
-  // more than 24 panels: launched schedule for the first block rows, one team launch for the rest (run_cholesky_hybrid)
-  if (team_ok && (c->team_fit > 0 || (c->team_fit < 0 && c->lookahead < 0 && c->aggregate <= 0)) && nb > whole_max && c->team_hybrid) {
-    const int rs = run_cholesky_hybrid(c, G_use > 1 ? G_use : 1);
-    if (rs <= 0) return rs;
-  }
-  if (G_use > 1 && nb >= 2 * G_use) {
-    for (int p0 = 0; p0 < nb; p0 += G_use) {
-      chol_group_step(c, p0, G_use, c->stream);
-      for (int p = p0; p < p0 + G_use && p < nb; ++p)
-        if (maybe_start_early_inverse(c, p)) return -1;
-    }
-    return 0;
-  }
-  for (int p = 0; p < nb; ++p) {
-    chol_group_step(c, p, 1, c->stream);
-    if (maybe_start_early_inverse(c, p)) return -1;
-  }
-  return 0;
 }
 
 // R = U^-1 (upper) by recursive doubling over the 128-blocks: the diagonal tiles are the E_p of the
@@ -559,7 +492,7 @@ static void merge_level(bocf_ctx* c, int lo, int w, int w2, int count, int which
     h.M = b2; h.Ncols = b1; h.K = b2; h.kb = BOCF_TILE; h.krt = BOCF_TILE; h.rt_desc = 1; h.alpha = -1.0; h.batch1 = m;
     // the three-buffer triangular kernel with its store epilogue (the product has the variance's shape) from 4096 rows: measured inverse 6.80 -> 6.53 ms
     // at N = 8192, but 1.47 -> 1.55 at N = 4096 (2048-row products: 512 workgroups of very unequal length on 256 CUs suit the smaller tiles better)
-    h.no_x3 = c->merge_x3 <= 0 || (c->merge_x3 == 1 && b2 < 4096);
+    h.no_x3 = c->chol.merge_x3 <= 0 || (c->chol.merge_x3 == 1 && b2 < 4096);
     h.swizzle = 2;
     launch_gemm_f64(h, m * count, 0, st);
     // R12 = RT21^T
@@ -572,13 +505,6 @@ static void copy_diag_range(bocf_ctx* c, int blk_lo, int blk_hi, hipStream_t st)
   const long strideS = (long)Np * Np, strideE = (long)nb * BOCF_TILE * BOCF_TILE;
   launch_copy_diag_blocks(wE(c), strideE, wR(c), strideS, Np, blk_lo, blk_hi, m, st);
   launch_copy_diag_blocks(wET(c), strideE, wRT(c), strideS, Np, blk_lo, blk_hi, m, st);
-}
-
-// split of the inverse: h = the largest power of two below nb; blocks [0, h) form complete pairs at every level below h
-static int trtri_split(int nb) {
-  int h = 1;
-  while (2 * h < nb) h *= 2;
-  return h;
 }
 
 // everything of the inverse that needs only block rows [0, h) of U: runs on `st` as soon as those rows are final

@@ -247,14 +247,11 @@ static int fit_sharded(bocf_ctx* c, const double* X, const double* Y, int N, int
     bocf_ctx* hctx = c->shard_helper;
     // the helper factorizes with the caller's schedule: every schedule option is forwarded and the schedule is chosen for the
     // GLOBAL output count, so a share is factorized by the very kernel sequence the replicated fit would run for that output
-    hctx->aggregate = c->aggregate; hctx->lookahead = c->lookahead; hctx->lookahead_min_nb = c->lookahead_min_nb;
-    hctx->overlap_inverse = c->overlap_inverse; hctx->potrf_scalar = c->potrf_scalar; hctx->team_fit = c->team_fit; hctx->team_panels = c->team_panels;
-    hctx->team_crit_load = c->team_crit_load; hctx->team_stream = c->team_stream;
-    hctx->trsm_wave = c->trsm_wave; hctx->merge_x3 = c->merge_x3; hctx->gated_off = c->gated_off;
+    hctx->chol = c->chol;
     hctx->sched_m = m;
-    // ... and with the caller's schedule HISTORY: whether CU masks work here, the pretended device size of the tests, and "not the first
-    // factorization of the context" (the first one always runs single-stream), so that helper and replicated fit pick the same kernels
-    hctx->cu_masks_ok = c->cu_masks_ok; hctx->force_cu_count = c->force_cu_count;
+    // ... and with the caller's schedule HISTORY: whether CU masks work here, time-outs, and "not the first factorization of the context"
+    // (the first one always runs single-stream), so that helper and replicated fit pick the same kernels
+    hctx->cu_masks_ok = c->cu_masks_ok; hctx->gated_off = c->gated_off;
     if (hctx->fits_done < c->fits_done) hctx->fits_done = c->fits_done;
     hctx->test_diag_shift = c->test_diag_shift;
     return fit_sharded_local(c, hctx, G, me, simulate, X, Y, N, d, m, kernel_id, variance, lengthscale, noise, max_jitter_tries, meta_w, meta_host);
@@ -390,12 +387,10 @@ extern "C" int bocf_fit(bocf_ctx* c, const double* X, const double* Y, int N, in
     HIPCHK(hipMemsetAsync(c->RT.p, 0, sizeof(double) * strideS * m, c->stream));
     c->zeroed_R = c->R.p; c->zeroed_RT = c->RT.p; c->zeroed_Np = Np; c->zeroed_m = m;
   }
-  if (c->overlap_inverse != 0 && !c->s_inv) {
+  if (c->chol.overlap_inverse != 0 && !c->s_inv) {
     // the early part of the inverse runs on its own stream; where the runtime allows CU masks it keeps off the CUs the
-    // diagonal-block kernel of the (unmasked) main stream then finds free
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, c->device));
-    const int ncu = prop.multiProcessorCount, words = (ncu + 31) / 32;
+    // diagonal-block kernel of the (unmasked) main stream then finds free (the device's own CU count: force_cu_count is for selection)
+    const int ncu = c->ncu, words = (ncu + 31) / 32;
     const int keep = 32;       // 4 CUs of every XCD: the row products of the chain (hundreds of small workgroups) need more room than the diagonal
                                // blocks alone; measured 8 / 32 / 64 / 96 kept: 7.06 / 7.00 / 6.98 / 7.00 ms at config 3, 32.9 / 32.0 / 32.4 at N = 8192
     std::vector<uint32_t> mask(words, 0u);
@@ -816,14 +811,14 @@ extern "C" int bocf_hmc(bocf_ctx* c, const double* X, const double* Y, int N, in
 
 // The device work of ONE inference at the hyper-parameters in c->hypd, enqueued on the context's stream without any host interaction:
 // what bocf_fit (attempt 0 of the ladder, no refinement / train mean) + bocf_lml_gradients launch.  Results: c->lml, c->gout, c->info.
-static int enqueue_inference(bocf_ctx* c) {
+static int enqueue_inference(bocf_ctx* c, const CholPlan& plan) {
   const int N = c->N, Np = c->Np, m = c->m, d = c->d;
   const long strideS = (long)Np * Np;
   // (the inputs were scaled, the schedule counters zeroed, by the PRE launch of hmc_stream_kernel; its POST launch takes the log-marginal
   //  and reduces the gradient partials)
   launch_build_train_kernel(c->Xs.as<double>(), c->xs_stride, N, Np, d, c->kernel_id, c->hypd.as<KernHyp>(), c->jit.as<double>(), 1,
                             c->S.as<double>(), strideS, m, c->stream, BOCF_KIDS(c));
-  if (bocf_run_cholesky(c)) return -1;
+  if (bocf_run_cholesky(c, &plan)) return -1;
   if (c->early_inverse_started) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_inv_early, 0));
   if (bocf_run_trtri(c, c->early_inverse_started != 0)) return -1;
   if (solve_alpha(c, false, false)) return -1;
@@ -913,24 +908,25 @@ extern "C" int bocf_hmc_streamed(bocf_ctx* c, const double* X, const double* Y, 
   a.X = c->X.as<double>(); a.Xs = c->Xs.as<double>(); a.strideXs = c->xs_stride; a.N = N; a.Np = c->Np;
   a.S = c->S.as<double>(); a.strideS = (long)c->Np * c->Np; a.alpha = c->alpha.as<double>(); a.yc = c->yc.as<double>();
   a.part = c->gpart.as<double>(); a.nblk = hypgrad_num_blocks(c->Np);
-  // the schedule of the fit above is the schedule of every factorization of the chain (same shape, same options); when it is the team
-  // schedule its counters are zeroed by the PRE launches instead of a memset node per step
-  a.flags = nullptr; a.flag_words = 0; a.sched_err = nullptr;
-  if (c->last_schedule == 3) {
-    a.flags = c->chol_flags.as<int>(); a.flag_words = c->chol_err_off / m; a.sched_err = a.flags + c->chol_err_off;
+  // every factorization of the chain runs ONE plan, made with what each of them sees (a fitted context, no redo pending); when it is the
+  // team schedule its counters are zeroed by the PRE launches instead of a memset node per step
+  CholPlan plan;
+  if (bocf_plan_cholesky(c, &plan)) return -1;
+  a.flags = nullptr; a.flag_words = 0;
+  a.sched_err = plan.flag_ints > 0 ? c->chol_flags.as<int>() + plan.err_off : nullptr;
+  if (plan.schedule == CHOL_TEAM_WHOLE) {
+    a.flags = c->chol_flags.as<int>(); a.flag_words = chol_team_flag_words(c->Np / BOCF_TILE);
     c->flags_device_zeroed = 1;
-  } else if (c->last_schedule == 2 || c->last_schedule == 4 || c->last_schedule == 5) {
-    a.sched_err = c->chol_flags.as<int>() + c->chol_err_off;
   }
   launch_hmc_stream(a, HS_INIT, 0, 0, c->stream);
-  if (enqueue_inference(c)) return -1;
+  if (enqueue_inference(c, plan)) return -1;
   launch_hmc_stream(a, HS_EVAL0, 0, 0, c->stream);
   const int check_every = 8;                               // draws between two looks at the abort word (a sync each)
   int aborted = -1;
   for (int i = 0; i < num_samples && aborted < 0; ++i) {
     for (int it = 0; it < hmc_iters; ++it) {
       launch_hmc_stream(a, HS_PRE, i, it, c->stream);
-      if (enqueue_inference(c)) return -1;
+      if (enqueue_inference(c, plan)) return -1;
       launch_hmc_stream(a, HS_POST, i, it, c->stream);
     }
     if ((i + 1) % check_every == 0 || i + 1 == num_samples) {

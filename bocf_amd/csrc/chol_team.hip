@@ -349,8 +349,7 @@ __device__ __attribute__((noinline)) void team_crit_stream(double* Sj_, const do
 #endif
 
 // counters of one output (ints): P[nb] | D[nb] | TR[nb][nb][2] | IR[nb][nb][2] | ST[nb] (row blocks of diagonal block p in memory) |
-// RD[nb] (units of panel p's critical set that carry every row before p)
-__host__ __device__ static inline int team_flag_words(int nb) { return ((4 * nb + 4 * nb * nb + 3) / 4) * 4; }
+// RD[nb] (units of panel p's critical set that carry every row before p); chol_team_flag_words(nb) (chol_plan.h) in all
 
 // (no __restrict__ / const on the matrices: other workgroups write them WHILE this one runs)
 __global__ __launch_bounds__(768, 1) void chol_team_kernel(TeamArgs a) {
@@ -653,8 +652,6 @@ __global__ __launch_bounds__(768, 1) void chol_team_kernel(TeamArgs a) {
     }
   }
 }
-
-int chol_team_flag_words(int nb) { return team_flag_words(nb); }
 
 // m outputs, T workgroups each; the caller has zeroed the counters and the error word on `s` and guarantees m * T <= compute units
 void launch_chol_team(const TeamArgs& a, int m, hipStream_t s) {

@@ -351,7 +351,8 @@ int bocf_profile_phase(bocf_ctx* ctx, const char* name, double* ms_out, long lon
 /* Counters and facts about the context (diagnostics; none of them changes a result).  Names: "sched_timeouts" = how often a
  * multi-stream factorization schedule ran into its 0.2 s dependency time-out and the attempt was redone on the single-stream
  * schedule (then "gated_schedules_off" = 1 for the rest of the context's life); "last_schedule" = schedule of the last
- * factorization (0 single stream, 2 reserved CUs);
+ * factorization (0 single stream, 2 reserved CUs, 3 one team launch, 4 team launches of panel groups, 5 hybrid: the first block rows
+ * launched or by team groups, one team launch for the rest);
  * "early_inverse";
  * "cu_masks_ok"; "comm_world" = ranks of the context's RCCL communicator (0 = none); "kstar_workspace_bytes". */
 int bocf_get_stat(bocf_ctx* ctx, const char* name, long long* value_out);

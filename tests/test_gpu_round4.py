@@ -88,6 +88,50 @@ def test_team_schedule_small_teams(B, probes, cus):
     np.testing.assert_allclose(team.predict(p["Xc"])[1], launched.predict(p["Xc"])[1], rtol=1e-7, atol=1e-12)
 
 
+def _against_oracle(p, model, kind="rbf"):
+    ref = R.MultiOutputGPRef(kind, p["variances"], p["lengthscales"], p["noise"])
+    ref.updateModel(p["X"], p["Y"])
+    rm, rv = ref.predict(p["Xc"])
+    mean, var = model.predict(p["Xc"])
+    np.testing.assert_allclose(mean, rm, rtol=1e-5, atol=1e-6)
+    assert np.abs(var - rv).max() <= 1e-5 * max(p["variances"]) + 1e-10
+
+
+# 25 panels is a hybrid size (team groups for the first 16 block rows, one team launch for the last 9), but on a device of 6 compute units
+# the tail's teams would be a single workgroup: the schedule is decided before anything is enqueued, so the fit runs the launched schedule
+# from the start -- the factor of a team_fit = 0 model bit for bit, no time-out, the oracle's posterior.
+def test_hybrid_without_tail_teams_runs_launched(B, probes):
+    N, d, m = 3200, 4, 2
+    p = R.synthetic_problem(N, d, m, 64, 8, 4343, noise=1e-4)
+    launched = _fit(B, "rbf", p, [("team_fit", 0)])
+    small = _fit(B, "rbf", p, [("force_cu_count", 6)], fits=2)
+    ctx = small._context()
+    assert ctx.stat("last_schedule") == 0 and ctx.stat("sched_timeouts") == 0
+    for j in range(m):
+        np.testing.assert_array_equal(small.get_factor(j)[0], launched.get_factor(j)[0])
+    _against_oracle(p, small)
+
+
+# A dependency time-out of the hybrid schedule (forced by the probes hook) at the real device size: the attempt is redone on the launched
+# schedule (the factor of a team_fit = 0 model bit for bit), counted once, and the next fit is the hybrid's again.
+def test_hybrid_time_out_is_redone_launched(B, probes):
+    N, d, m = 3200, 4, 2
+    p = R.synthetic_problem(N, d, m, 64, 8, 4343, noise=1e-4)
+    launched = _fit(B, "rbf", p, [("team_fit", 0)])
+    model = _fit(B, "rbf", p, [])
+    ctx = model._context()
+    assert ctx.stat("last_schedule") == 5 and ctx.stat("sched_timeouts") == 0
+    model.set_option("force_sched_timeout", 1)
+    model.updateModel(p["X"], p["Y"])
+    assert ctx.stat("sched_timeouts") == 1 and ctx.stat("last_schedule") == 0
+    for j in range(m):
+        np.testing.assert_array_equal(model.get_factor(j)[0], launched.get_factor(j)[0])
+    _against_oracle(p, model)
+    model.updateModel(p["X"], p["Y"])
+    assert ctx.stat("sched_timeouts") == 1 and ctx.stat("last_schedule") == 5
+    _against_oracle(p, model)
+
+
 # The jitter ladder through the team schedule (linalg.py:52-71): the device reports the first bad pivot per output, the host climbs the
 # ladder and re-launches; and a dependency time-out (forced by the probes hook) sends the attempt back to the launched schedule.
 def test_team_schedule_jitter_ladder_and_fallback(B, probes):
