@@ -12,8 +12,8 @@
 int bocf_fail(const char* what, const char* detail);      // records bocf_last_error(), returns -1
 void bocf_set_error(const char* text);                    // records bocf_last_error() verbatim (positive LAPACK-style returns)
 int bocf_launch_status();
-int bocf_plan_cholesky(bocf_ctx* c, CholPlan* out);       // capi_chol.hip: the schedule of the next factorization, its streams and counters
-int bocf_run_cholesky(bocf_ctx* c, const CholPlan* plan = nullptr);   // blocked Cholesky of all outputs (nullptr: planned here)
+int bocf_plan_cholesky(bocf_ctx* c, bool kinv, CholPlan* out);   // capi_chol.hip: the schedule of the next factorization (kinv: Ky^-1 wanted), its streams and counters
+int bocf_run_cholesky(bocf_ctx* c, const CholPlan& plan, bool counters_zeroed = false);   // blocked Cholesky of all outputs (counters_zeroed: by the caller's kernels)
 int bocf_run_trtri(bocf_ctx* c, bool early_done);         // capi_chol.hip: R = U^-1 (the part the factorization did not already start)
 int bocf_comm_broadcast(bocf_ctx* c, double* buf, size_t count, int root);   // comm.hip: ncclBroadcast on the context's stream
 int bocf_comm_group(bool start);                                             // ncclGroupStart / ncclGroupEnd
@@ -87,9 +87,7 @@ struct bocf_ctx {
   int chol_flags_used = 0;
   int chol_err_off = 0;      // index of the time-out word inside chol_flags (from the plan of the last factorization)
   CholOptions chol;          // the factorization-schedule options (chol_plan.h)
-  int flags_device_zeroed = 0;   // the caller's kernels zero the team schedule's counters in front of every factorization (stream-resident HMC)
-  int want_kinv = 0;         // the caller is an INFERENCE (bocf_lml_gradients follows): a schedule that can, leaves Ky^-1 in the T scratch
-  int kinv_done = 0;         // ... and did
+  int kinv_done = 0;         // the factorization schedule left Ky^-1 in the T scratch (an inference asked for it, bocf_plan_cholesky)
   int inverse_done = 0;      // the factorization schedule already produced R and R^T (team schedule)
   int ncu = 0;               // compute units of the device (read once, by bocf_create)
   unsigned long long* team_tl = nullptr;   // probes build: task timeline of the team kernel (tools/team_timeline.py)

@@ -388,11 +388,12 @@ static int run_cholesky_launched(bocf_ctx* c, const CholPlan& plan) {
 
 // The schedule of the next factorization of c (chol_plan.h) and what it needs: the reserved-CU streams, the counter block.  The one
 // refusal the runtime may still make -- CU masks (hipExtStreamCreateWithCUMask) -- comes before anything is enqueued and is planned round.
-int bocf_plan_cholesky(bocf_ctx* c, CholPlan* out) {
+// kinv: the caller is an inference (bocf_lml_gradients follows), a schedule that can, leaves Ky^-1 in the T scratch.
+int bocf_plan_cholesky(bocf_ctx* c, bool kinv, CholPlan* out) {
   CholPlanInput in;
   in.nb = c->Np / BOCF_TILE; in.m = c->m; in.sched_m = c->sched_m; in.ncu = c->ncu;
   in.inv_stream = c->s_inv != nullptr; in.cu_masks_ok = c->cu_masks_ok; in.gated_off = c->gated_off; in.sched_retry = c->sched_retry;
-  in.refit = c->fits_done > 0; in.want_kinv = c->want_kinv;
+  in.refit = c->fits_done > 0; in.want_kinv = kinv;
   c->sched_retry = 0;
   CholPlan plan = plan_cholesky(in, c->chol);
   if (plan.schedule == CHOL_RESERVED) {
@@ -408,7 +409,7 @@ int bocf_plan_cholesky(bocf_ctx* c, CholPlan* out) {
   return 0;
 }
 
-static int run_cholesky_impl(bocf_ctx* c, const CholPlan& plan) {
+static int run_cholesky_impl(bocf_ctx* c, const CholPlan& plan, bool counters_zeroed) {
   c->early_inverse_started = 0;
   c->inverse_done = 0;
   c->kinv_done = 0;
@@ -416,8 +417,9 @@ static int run_cholesky_impl(bocf_ctx* c, const CholPlan& plan) {
   c->chol_flags_used = plan.flag_ints > 0 ? 1 : 0;
   c->chol_err_off = plan.err_off;
   set_potrf_scalar(c->chol.potrf_scalar);                // (probes build: timing-only variants of the diagonal-block kernel)
-  // the counters and the time-out word, zeroed ONCE per factorization (for the team schedule of a stream-resident HMC chain its kernels do it)
-  if (plan.flag_ints > 0 && !c->flags_device_zeroed) HIPCHK(hipMemsetAsync(c->chol_flags.p, 0, sizeof(int) * plan.flag_ints, c->stream));
+  // the counters and the time-out word, zeroed ONCE per factorization (unless the caller's kernels do it: the team schedule of a
+  // stream-resident HMC chain)
+  if (plan.flag_ints > 0 && !counters_zeroed) HIPCHK(hipMemsetAsync(c->chol_flags.p, 0, sizeof(int) * plan.flag_ints, c->stream));
   const int nb = c->Np / BOCF_TILE;
   switch (plan.schedule) {
     case CHOL_TEAM_WHOLE: return run_cholesky_team(c, plan, 0, nb, 0, plan.T);
@@ -429,21 +431,18 @@ static int run_cholesky_impl(bocf_ctx* c, const CholPlan& plan) {
   return run_cholesky_launched(c, plan);
 }
 
-int bocf_run_cholesky(bocf_ctx* c, const CholPlan* chain_plan) {
-  CholPlan plan;
-  if (chain_plan) plan = *chain_plan;
-  else if (bocf_plan_cholesky(c, &plan)) return -1;
+int bocf_run_cholesky(bocf_ctx* c, const CholPlan& plan, bool counters_zeroed) {
 #ifdef BOCF_PROBES
   const char* tl = getenv("BOCF_DBG_TL");                // plain-run timeline of the chain kernels (tools/dbg_timeline.py)
   if (tl) {
     HIPCHK(hipStreamSynchronize(c->stream));
     dbg_tl_start();
   }
-  const int rc = run_cholesky_impl(c, plan);
+  const int rc = run_cholesky_impl(c, plan, counters_zeroed);
   if (tl && rc == 0) dbg_tl_dump(tl);
   return rc;
 #else
-  return run_cholesky_impl(c, plan);
+  return run_cholesky_impl(c, plan, counters_zeroed);
 #endif
 }
 

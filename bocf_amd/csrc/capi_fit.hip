@@ -39,6 +39,69 @@ extern "C" int bocf_set_kernel_ids(bocf_ctx* c, const int* ids, int m) {
   return 0;
 }
 
+// The host arguments of a fit: inputs X (N, d), targets Y (m, N), the kernel family, per-output variance (m), lengthscales (m, d), noise (m).
+struct FitInput {
+  const double *X, *Y;
+  int N, d, m, kernel_id;
+  const double *variance, *lengthscale, *noise;
+};
+
+// What one replicated fit is for.  bocf_fit takes it from the options; an inference states its own.
+struct FitSettings {
+  bool want_kinv = false;   // an inference (bocf_lml_gradients follows): a schedule that can, leaves Ky^-1 in the T scratch
+  bool refine = true;       // refine alpha and refresh the posterior mean at the training inputs (not option skip_mu_train)
+  bool reuse = false;       // option reuse_data: X and Y are resident from the previous fit, only the hyper-parameters are uploaded
+};
+
+// ... as the options ask for it (reuse_data, skip_mu_train)
+static FitSettings option_settings(const bocf_ctx* c, bool want_kinv) { return {want_kinv, !c->skip_mu_train, c->reuse_data != 0}; }
+
+// The argument checks of bocf_fit and bocf_infer (`who`).
+static int check_fit_input(bocf_ctx* c, const char* who, const FitInput& in) {
+  if (!c || !in.X || !in.Y || !in.variance || !in.lengthscale || !in.noise) return drop_kernel_ids(c, fail(who, "null argument"));
+  if (in.N < 1 || in.d < 1 || in.d > BOCF_MAX_D || in.m < 1 || in.m > BOCF_MAX_FITS) return drop_kernel_ids(c, fail(who, "N, d or m out of range"));
+  if (in.kernel_id < 0 || in.kernel_id > 3) return drop_kernel_ids(c, fail(who, "unknown kernel id"));
+  for (int j = 0; j < in.m; ++j) {
+    if (!(in.variance[j] > 0.0) || !(in.noise[j] >= 0.0)) return drop_kernel_ids(c, fail(who, "variance must be > 0 and noise >= 0"));
+    for (int q = 0; q < in.d; ++q)
+      if (!(in.lengthscale[(long)j * in.d + q] > 0.0)) return drop_kernel_ids(c, fail(who, "lengthscale must be > 0"));
+  }
+  return 0;
+}
+
+// A new resident model of in's shape: the previous fit and everything derived from it are gone, the pending kernel ids are taken.
+static int begin_model(bocf_ctx* c, const FitInput& in) {
+  c->fitted = false; c->canned = false; c->sharded = false; c->have_acq = false; c->r32_valid = false; c->ri8_valid = false;
+  c->N = in.N; c->Np = round_up(in.N, BOCF_TILE); c->d = in.d; c->m = in.m; c->kernel_id = in.kernel_id;
+  c->xs_stride = (long)c->Np * in.d;
+  return take_kernel_ids(c, in.m);
+}
+
+// jitchol's ladder (GPy/util/linalg.py:52-71): the first failing output's info (0: every output factorized) ...
+static int first_failure(const std::vector<int>& info) {
+  for (int v : info)
+    if (v != 0) return v;
+  return 0;
+}
+
+// ... the next rung for every output that failed: 1e-6 mean(diag(Ky)), then ten times the last ...
+static void next_rung(bocf_ctx* c, const std::vector<int>& info) {
+  for (int j = 0; j < c->m; ++j)
+    if (info[j] != 0) {
+      const double diag_mean = c->hyp[j].variance + c->hyp[j].noise + 1e-8 - c->test_diag_shift;   // mean(diag(Ky)), stationary kernel
+      c->jitter[j] = c->jitter[j] == 0.0 ? diag_mean * 1e-6 : c->jitter[j] * 10.0;
+    }
+}
+
+// ... and its outcome: jitter and status recorded, a positive info when some output stayed indefinite
+static int end_ladder(bocf_ctx* c, const std::vector<int>& info, double* jitter_out) {
+  if (jitter_out) memcpy(jitter_out, c->jitter.data(), sizeof(double) * c->m);
+  c->last_info = info;
+  const int bad = first_failure(info);
+  if (bad) bocf_set_error("not positive definite, even with jitter.");
+  return bad;
+}
+
 // alpha = Ky^-1 yc = R (R^T yc) (exact_gaussian_inference.py:51), the log-marginal (:53) and -- unless the caller is an
 // inference of a hyper-parameter update, which reads neither -- ONE step of iterative refinement with the residual yc - Ky alpha
 // carried in double-double, and the posterior mean at the training inputs (multi_outputGP.py:176-180) as yc + ymean - dg alpha.
@@ -70,8 +133,6 @@ static int solve_alpha(bocf_ctx* c, bool refine_and_train_mean, bool with_lml = 
   return 0;
 }
 
-// X, the centred targets and the hyper-parameters onto the device (X, yc, hypd must be allocated).  With option
-// "reuse_data" only the hyper-parameters move: X and Y are those of the previous call (same N, d, m).
 // Host-to-device copies of a fit's small inputs through ONE pinned arena (a copy out of pageable memory is staged and waited for by the
 // runtime, one after the other): the caller memcpy's into the slot and the copy is asynchronous.  The arena is free again at the fit's one
 // stream synchronisation; slots of one fit do not overlap.  Returns nullptr when the arena cannot hold `bytes` at `off` (pageable path).
@@ -95,59 +156,68 @@ static char* fit_arena(bocf_ctx* c, size_t off, size_t bytes) {
   return static_cast<char*>(c->up_pin) + off;
 }
 
-static int stage_data(bocf_ctx* c, const double* X, const double* Y, int N, int Np, int d, int m, const double* variance,
-                      const double* lengthscale, const double* noise) {
-  const bool reuse = c->reuse_data && c->data_N == N && c->data_d == d && c->data_m == m && (int)c->hyp.size() == m;
-  if (c->reuse_data && !reuse) return fail("bocf_fit / bocf_infer", "option reuse_data is set but N, d or m differ from the previous fit");
+// the X / Y resident on the device have in's shape
+static bool data_resident(const bocf_ctx* c, const FitInput& in) {
+  return c->data_N == in.N && c->data_d == in.d && c->data_m == in.m && (int)c->hyp.size() == in.m;
+}
+
+// Standardize: subtract the mean only (normalizer.py:57-70).  Returns the centred targets (m, Np; zero padding), the means go to c->hyp.
+static std::vector<double> centre_targets(bocf_ctx* c, const double* Y, int N, int Np, int m) {
+  std::vector<double> yc((size_t)m * Np, 0.0);
+  for (int j = 0; j < m; ++j) {
+    double s = 0.0;
+    for (int i = 0; i < N; ++i) s += Y[(long)j * N + i];
+    const double mean = s / N;
+    c->hyp[j].ymean = mean;
+    for (int i = 0; i < N; ++i) yc[(long)j * Np + i] = Y[(long)j * N + i] - mean;
+  }
+  return yc;
+}
+
+// X, the centred targets and the hyper-parameters onto the device (begin_model was called; X, yc, hypd must be allocated).  With `reuse`
+// (option reuse_data) only the hyper-parameters move: X and Y are those of the previous call, which must have had the same N, d, m.
+static int stage_data(bocf_ctx* c, const FitInput& in, bool reuse) {
+  const int N = in.N, Np = c->Np, d = in.d, m = in.m;
+  if (reuse && !data_resident(c, in)) return fail("bocf_fit / bocf_infer", "option reuse_data is set but N, d or m differ from the previous fit");
+  if (!reuse) c->hyp.assign(m, KernHyp());
+  for (int j = 0; j < m; ++j) {
+    KernHyp& h = c->hyp[j];
+    h.variance = in.variance[j]; h.noise = in.noise[j]; h.jitter = -c->test_diag_shift;
+    for (int q = 0; q < BOCF_MAX_D; ++q) h.ls[q] = q < d ? in.lengthscale[(long)j * d + q] : 1.0;
+  }
   if (reuse) {
     // same X and targets as the previous fit (HMC / optimiser inferences): only the hyper-parameters are uploaded
-    for (int j = 0; j < m; ++j) {
-      KernHyp& h = c->hyp[j];
-      h.variance = variance[j]; h.noise = noise[j]; h.jitter = -c->test_diag_shift;
-      for (int q = 0; q < BOCF_MAX_D; ++q) h.ls[q] = q < d ? lengthscale[(long)j * d + q] : 1.0;
-    }
     HIPCHK(hipMemcpyAsync(c->hypd.p, c->hyp.data(), sizeof(KernHyp) * m, hipMemcpyHostToDevice, c->stream));   // c->hyp outlives the copy
     c->arena_used = 0;
-  } else {
-    // Standardize: subtract the mean only (normalizer.py:57-70)
-    c->hyp.assign(m, KernHyp());
-    std::vector<double> yc((size_t)m * Np, 0.0);
-    for (int j = 0; j < m; ++j) {
-      double s = 0.0;
-      for (int i = 0; i < N; ++i) s += Y[(long)j * N + i];
-      const double mean = s / N;
-      KernHyp& h = c->hyp[j];
-      h.variance = variance[j]; h.noise = noise[j]; h.ymean = mean; h.jitter = -c->test_diag_shift;
-      for (int q = 0; q < BOCF_MAX_D; ++q) h.ls[q] = q < d ? lengthscale[(long)j * d + q] : 1.0;
-      for (int i = 0; i < N; ++i) yc[(long)j * Np + i] = Y[(long)j * N + i] - mean;
-    }
-    // one pinned arena: [X | hyper-parameters | centred targets | (jitter, in the ladder loop)] -- asynchronous copies, no synchronisation here
-    const size_t bX = sizeof(double) * (size_t)N * d, bH = ((sizeof(KernHyp) * m + 63) / 64) * 64, bY = sizeof(double) * (size_t)m * Np;
-    char* ar = fit_arena(c, 0, bX + bH + bY + 64 * (size_t)m);
-    if (ar) {
-      memcpy(ar, X, bX);
-      memcpy(ar + bX, c->hyp.data(), sizeof(KernHyp) * m);
-      memcpy(ar + bX + bH, yc.data(), bY);
-      HIPCHK(hipMemcpyAsync(c->X.p, ar, bX, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(hipMemcpyAsync(c->hypd.p, ar + bX, sizeof(KernHyp) * m, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(hipMemcpyAsync(c->yc.p, ar + bX + bH, bY, hipMemcpyHostToDevice, c->stream));
-      c->arena_used = bX + bH + bY;
-    } else {
-      HIPCHK(hipMemcpyAsync(c->X.p, X, bX, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(hipMemcpyAsync(c->hypd.p, c->hyp.data(), sizeof(KernHyp) * m, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(hipMemcpyAsync(c->yc.p, yc.data(), bY, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));   // host staging buffers go out of scope below
-      c->arena_used = 0;
-    }
-    c->data_N = N; c->data_d = d; c->data_m = m;
+    return 0;
   }
+  const std::vector<double> yc = centre_targets(c, in.Y, N, Np, m);
+  // one pinned arena: [X | hyper-parameters | centred targets | (jitter, in the ladder loop)] -- asynchronous copies, no synchronisation here
+  const size_t bX = sizeof(double) * (size_t)N * d, bH = ((sizeof(KernHyp) * m + 63) / 64) * 64, bY = sizeof(double) * (size_t)m * Np;
+  char* ar = fit_arena(c, 0, bX + bH + bY + 64 * (size_t)m);
+  if (ar) {
+    memcpy(ar, in.X, bX);
+    memcpy(ar + bX, c->hyp.data(), sizeof(KernHyp) * m);
+    memcpy(ar + bX + bH, yc.data(), bY);
+    HIPCHK(hipMemcpyAsync(c->X.p, ar, bX, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->hypd.p, ar + bX, sizeof(KernHyp) * m, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->yc.p, ar + bX + bH, bY, hipMemcpyHostToDevice, c->stream));
+    c->arena_used = bX + bH + bY;
+  } else {
+    HIPCHK(hipMemcpyAsync(c->X.p, in.X, bX, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->hypd.p, c->hyp.data(), sizeof(KernHyp) * m, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->yc.p, yc.data(), bY, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   // host staging buffers go out of scope below
+    c->arena_used = 0;
+  }
+  c->data_N = N; c->data_d = d; c->data_m = m;
   return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Output-sharded fit (SURVEY 8e "better"): the m factorizations are independent (multi_outputGP.py:64-95 builds one GPModel
 // per output, :97-102 updates them one after the other), so rank r of G factorizes only the outputs of its contiguous
-// share [j0, j1) -- with the ordinary bocf_fit, in a helper context on the same GPU -- and the ranks then exchange what
+// share [j0, j1) -- with the replicated fit, in a helper context on the same GPU -- and the ranks then exchange what
 // PREDICTION needs: the inverse factor R_j (broadcast from its owner over xGMI, the m broadcasts in one RCCL group) and the
 // small per-output vectors alpha_j, mean at the training inputs, log-marginal, jitter, status (every element has exactly one
 // owner, the others hold zeros: ONE all-reduce(SUM)).  R^T (the k-major operand of the gradient path) is rebuilt locally by
@@ -160,27 +230,29 @@ static void shard_range(int m, int G, int r, int* j0, int* j1) {
   *j1 = *j0 + base + (r < rem ? 1 : 0);
 }
 
-// The local share of a sharded fit: this rank's outputs through the ordinary bocf_fit of the helper context, results copied into
+static int fit_replicated(bocf_ctx* c, const FitInput& in, const FitSettings& s, int max_jitter_tries, double* jitter_out, double* lml_out);
+
+// The local share of a sharded fit: this rank's outputs through the replicated fit of the helper context, results copied into
 // R and the meta block.  Any failure comes back as -1 (error text recorded) WITHOUT returning from fit_sharded: the caller must still
 // take part in the collectives, or every peer would wait for this rank forever.
-static int fit_sharded_local(bocf_ctx* c, bocf_ctx* hctx, int G, int me, int simulate, const double* X, const double* Y, int N, int d, int m,
-                             int kernel_id, const double* variance, const double* lengthscale, const double* noise, int max_jitter_tries,
+static int fit_sharded_local(bocf_ctx* c, bocf_ctx* hctx, int G, int me, int simulate, const FitInput& in, int max_jitter_tries,
                              size_t meta_w, std::vector<double>& meta_host) {
-  const int Np = c->Np;
+  const int N = in.N, Np = c->Np;
   const long strideS = (long)Np * Np;
   for (int r = 0; r < G; ++r) {
     if (!simulate && r != me) continue;
     int j0, j1;
-    shard_range(m, G, r, &j0, &j1);
+    shard_range(in.m, G, r, &j0, &j1);
     const int ml = j1 - j0;
     if (ml <= 0) continue;
     std::vector<double> jit(ml, 0.0), lml(ml, 0.0);
     if (BOCF_KIDS(c)) hctx->pending_ids.assign(c->kernel_ids.begin() + j0, c->kernel_ids.begin() + j1);   // the share's kernel families
-    // INVARIANT: bocf_fit on the helper is synchronous (its stream is idle on return) and the copies below run on c->stream; with
+    FitInput share = in;
+    share.Y += (size_t)j0 * N; share.m = ml; share.variance += j0; share.lengthscale += (size_t)j0 * in.d; share.noise += j0;
+    // INVARIANT: the helper's fit is synchronous (its stream is idle on return) and the copies below run on c->stream; with
     // more than one share per process (the simulate hook) c->stream is drained before the helper refits, because that refit
     // rewrites the buffers the copies read.
-    const int rc = bocf_fit(hctx, X, Y + (size_t)j0 * N, N, d, ml, kernel_id, variance + j0, lengthscale + (size_t)j0 * d, noise + j0,
-                            max_jitter_tries, jit.data(), lml.data());
+    const int rc = fit_replicated(hctx, share, FitSettings{}, max_jitter_tries, jit.data(), lml.data());
     if (rc < 0) return -1;
     HIPCHK(hipSetDevice(c->device));
     std::vector<int> info(ml, 0);
@@ -209,16 +281,12 @@ static int fit_sharded_local(bocf_ctx* c, bocf_ctx* hctx, int G, int me, int sim
   return 0;
 }
 
-static int fit_sharded(bocf_ctx* c, const double* X, const double* Y, int N, int d, int m, int kernel_id, const double* variance,
-                       const double* lengthscale, const double* noise, int max_jitter_tries, double* jitter_out, double* lml_out) {
+static int fit_sharded(bocf_ctx* c, const FitInput& in, int max_jitter_tries, double* jitter_out, double* lml_out) {
   const int simulate = c->shard_fit_simulate;                 // test hook (BOCF_PROBES builds): one process plays all G ranks in turn, no collectives
   const int G = simulate > 0 ? simulate : (c->comm ? c->world : 1), me = simulate > 0 ? 0 : (c->comm ? c->rank : 0);
-  c->fitted = false; c->canned = false; c->have_acq = false; c->r32_valid = false; c->ri8_valid = false;
-  const int Np = round_up(N, BOCF_TILE), nb = Np / BOCF_TILE;
-  c->N = N; c->Np = Np; c->d = d; c->m = m; c->kernel_id = kernel_id;
-  const int ids_rc = take_kernel_ids(c, m);                   // (a mismatch is reported from the local phase: nothing returns before the exchange)
+  const int ids_rc = begin_model(c, in);                      // (a mismatch is reported from the local phase: nothing returns before the exchange)
+  const int N = in.N, d = in.d, m = in.m, Np = c->Np, nb = Np / BOCF_TILE;
   const long strideS = (long)Np * Np;
-  c->xs_stride = (long)Np * d;
   const size_t meta_w = (size_t)Np + N + 4;                   // alpha | train mean | lml, jitter, info, owner-count
   const size_t meta_n = (size_t)m * meta_w + 2;               // + number of ranks whose local share failed (+ padding)
   const size_t tiles = (size_t)nb * (nb + 1) / 2, packed = tiles * BOCF_TILE * BOCF_TILE;    // the exchanged part of one inverse factor
@@ -241,7 +309,7 @@ static int fit_sharded(bocf_ctx* c, const double* X, const double* Y, int N, int
     // only the tiles on / above the diagonal of R are ever written (by the owner's fit or by the unpacking below): the other half
     // must be zeros, so a buffer that is new or was laid out for another size is cleared first
     if (c->zeroed_R != c->R.p || c->zeroed_Np != Np || c->zeroed_m < m) HIPCHK(hipMemsetAsync(c->R.p, 0, sizeof(double) * strideS * m, c->stream));
-    if (stage_data(c, X, Y, N, Np, d, m, variance, lengthscale, noise)) return -1;
+    if (stage_data(c, in, false)) return -1;               // (a sharded fit is never taken with option reuse_data)
     launch_scale_inputs(c->X.as<double>(), N, d, c->hypd.as<KernHyp>(), m, c->Xs.as<double>(), c->xs_stride, c->stream);
     if (!c->shard_helper && bocf_create(c->device, &c->shard_helper)) return -1;
     bocf_ctx* hctx = c->shard_helper;
@@ -254,7 +322,7 @@ static int fit_sharded(bocf_ctx* c, const double* X, const double* Y, int N, int
     hctx->cu_masks_ok = c->cu_masks_ok; hctx->gated_off = c->gated_off;
     if (hctx->fits_done < c->fits_done) hctx->fits_done = c->fits_done;
     hctx->test_diag_shift = c->test_diag_shift;
-    return fit_sharded_local(c, hctx, G, me, simulate, X, Y, N, d, m, kernel_id, variance, lengthscale, noise, max_jitter_tries, meta_w, meta_host);
+    return fit_sharded_local(c, hctx, G, me, simulate, in, max_jitter_tries, meta_w, meta_host);
   };
   local_rc = local();
   if (local_rc < 0) local_err = bocf_last_error();
@@ -320,20 +388,15 @@ static int fit_sharded(bocf_ctx* c, const double* X, const double* Y, int N, int
   LAUNCHCHK();
   c->jitter.assign(m, 0.0);
   c->last_info.assign(m, 0);
-  int bad = 0;
   std::vector<double> lml(m);
   for (int j = 0; j < m; ++j) {
     if (tail[(size_t)j * 4 + 3] != 1.0) return fail("bocf_fit (sharded)", "an output was factorized by no rank or by several");
     lml[j] = tail[(size_t)j * 4];
     c->jitter[j] = tail[(size_t)j * 4 + 1];
     c->last_info[j] = (int)tail[(size_t)j * 4 + 2];
-    if (c->last_info[j] != 0 && bad == 0) bad = c->last_info[j];
   }
   if (jitter_out) memcpy(jitter_out, c->jitter.data(), sizeof(double) * m);
-  if (bad) {
-    bocf_fail("bocf_fit", "not positive definite, even with jitter.");
-    return bad;
-  }
+  if (const int bad = first_failure(c->last_info)) return bocf_fail("bocf_fit", "not positive definite, even with jitter."), bad;
   HIPCHK(hipMemcpyAsync(c->lml.p, lml.data(), sizeof(double) * m, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (lml_out) memcpy(lml_out, lml.data(), sizeof(double) * m);
@@ -344,29 +407,12 @@ static int fit_sharded(bocf_ctx* c, const double* X, const double* Y, int N, int
   return 0;
 }
 
-extern "C" int bocf_fit(bocf_ctx* c, const double* X, const double* Y, int N, int d, int m, int kernel_id, const double* variance,
-                        const double* lengthscale, const double* noise, int max_jitter_tries, double* jitter_out, double* lml_out) {
-  if (!c || !X || !Y || !variance || !lengthscale || !noise) return drop_kernel_ids(c, fail("bocf_fit", "null argument"));
-  if (N < 1 || d < 1 || d > BOCF_MAX_D || m < 1 || m > BOCF_MAX_FITS) return drop_kernel_ids(c, fail("bocf_fit", "N, d or m out of range"));
-  if (kernel_id < 0 || kernel_id > 3) return drop_kernel_ids(c, fail("bocf_fit", "unknown kernel id"));
-  for (int j = 0; j < m; ++j) {
-    if (!(variance[j] > 0.0) || !(noise[j] >= 0.0)) return drop_kernel_ids(c, fail("bocf_fit", "variance must be > 0 and noise >= 0"));
-    for (int q = 0; q < d; ++q)
-      if (!(lengthscale[(long)j * d + q] > 0.0)) return drop_kernel_ids(c, fail("bocf_fit", "lengthscale must be > 0"));
-  }
-  if ((c->shard_fit && (c->comm || c->shard_fit_simulate > 0)) && !c->reuse_data && m > 1 && m % c->hyper_samples == 0)
-    return fit_sharded(c, X, Y, N, d, m, kernel_id, variance, lengthscale, noise, max_jitter_tries, jitter_out, lml_out);
+// The fit of all m outputs on this device (in was checked): stage, factorize with jitchol's ladder, invert, solve for alpha.
+static int fit_replicated(bocf_ctx* c, const FitInput& in, const FitSettings& s, int max_jitter_tries, double* jitter_out, double* lml_out) {
   HIPCHK(hipSetDevice(c->device));
-  c->fitted = false;
-  c->canned = false;
-  c->sharded = false;
-  c->have_acq = false;
-  c->r32_valid = false; c->ri8_valid = false;
-  const int Np = round_up(N, BOCF_TILE), nb = Np / BOCF_TILE;
-  c->N = N; c->Np = Np; c->d = d; c->m = m; c->kernel_id = kernel_id;
-  if (take_kernel_ids(c, m)) return -1;
+  if (begin_model(c, in)) return -1;
+  const int N = in.N, d = in.d, m = in.m, Np = c->Np, nb = Np / BOCF_TILE;
   const long strideS = (long)Np * Np;
-  c->xs_stride = (long)Np * d;
   if (c->X.ensure(sizeof(double) * (size_t)Np * d) || c->Xs.ensure(sizeof(double) * (size_t)m * Np * d) ||
       c->S.ensure(sizeof(double) * strideS * m) || c->R.ensure(sizeof(double) * strideS * m) ||
       c->E.ensure(sizeof(double) * (size_t)m * nb * BOCF_TILE * BOCF_TILE) ||
@@ -378,7 +424,7 @@ extern "C" int bocf_fit(bocf_ctx* c, const double* X, const double* Y, int N, in
       c->meanpart.ensure(sizeof(double) * (size_t)2 * m * nb * Np))
     return -1;
 
-  if (stage_data(c, X, Y, N, Np, d, m, variance, lengthscale, noise)) return -1;
+  if (stage_data(c, in, s.reuse)) return -1;
   launch_scale_inputs(c->X.as<double>(), N, d, c->hypd.as<KernHyp>(), m, c->Xs.as<double>(), c->xs_stride, c->stream);
   // R (upper) and R^T (lower) are rewritten block by block by every fit; their other triangles are zeros that nothing ever
   // writes, so they are cleared only when the buffers are new or laid out for another padded size
@@ -408,7 +454,8 @@ extern "C" int bocf_fit(bocf_ctx* c, const double* X, const double* Y, int N, in
   // jitchol ladder (GPy/util/linalg.py:52-71)
   c->jitter.assign(m, 0.0);
   std::vector<int> info(m, 0);
-  int bad = 0;
+  // status words and the log-marginal through one pinned block: [info (m ints) | schedule error word | pad] [log-marginal (m doubles)]
+  const size_t ioff = ((sizeof(int) * (m + 1) + 7) / 8) * 8, pbytes = ioff + sizeof(double) * m;
   for (int attempt = 0;; ++attempt) {
     std::vector<double> jeff(c->jitter);
     for (int j = 0; j < m; ++j) jeff[j] -= c->test_diag_shift;
@@ -420,12 +467,13 @@ extern "C" int bocf_fit(bocf_ctx* c, const double* X, const double* Y, int N, in
     HIPCHK(hipMemsetAsync(c->info.p, 0, sizeof(int) * m, c->stream));
     {
       PhaseTimer t(c, "kbuild");
-      launch_build_train_kernel(c->Xs.as<double>(), c->xs_stride, N, Np, d, kernel_id, c->hypd.as<KernHyp>(), c->jit.as<double>(), 1,
+      launch_build_train_kernel(c->Xs.as<double>(), c->xs_stride, N, Np, d, in.kernel_id, c->hypd.as<KernHyp>(), c->jit.as<double>(), 1,
                                 c->S.as<double>(), strideS, m, c->stream, BOCF_KIDS(c));
     }
     {
       PhaseTimer t(c, "cholesky");
-      if (bocf_run_cholesky(c)) return -1;
+      CholPlan plan;
+      if (bocf_plan_cholesky(c, s.want_kinv, &plan) || bocf_run_cholesky(c, plan)) return -1;
       // (a failed attempt is rebuilt from scratch: the early inverse must be off the buffers first -- the wait costs nothing
       //  when the attempt succeeded, the inverse phase would wait for the same event)
       if (c->early_inverse_started) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_inv_early, 0));
@@ -440,10 +488,8 @@ extern "C" int bocf_fit(bocf_ctx* c, const double* X, const double* Y, int N, in
     }
     {
       PhaseTimer t_alpha(c, "alpha");
-      if (solve_alpha(c, !c->skip_mu_train)) return -1;
+      if (solve_alpha(c, s.refine)) return -1;
     }
-    // status words and the log-marginal through one pinned block: [info (m ints) | schedule error word | pad] [log-marginal (m doubles)]
-    const size_t ioff = ((sizeof(int) * (m + 1) + 7) / 8) * 8, pbytes = ioff + sizeof(double) * m;
     if (c->fit_pin_cap < pbytes) {
       if (c->fit_pin) (void)hipHostFree(c->fit_pin);
       c->fit_pin = nullptr; c->fit_pin_cap = 0;
@@ -486,42 +532,30 @@ extern "C" int bocf_fit(bocf_ctx* c, const double* X, const double* Y, int N, in
       --attempt;
       continue;
     }
-    bad = 0;
-    for (int j = 0; j < m; ++j)
-      if (info[j] != 0 && bad == 0) bad = info[j];
-    if (!bad) break;
-    if (attempt >= max_jitter_tries) break;
-    for (int j = 0; j < m; ++j)
-      if (info[j] != 0) {
-        const double diag_mean = c->hyp[j].variance + c->hyp[j].noise + 1e-8 - c->test_diag_shift;   // mean(diag(Ky)), stationary kernel
-        c->jitter[j] = c->jitter[j] == 0.0 ? diag_mean * 1e-6 : c->jitter[j] * 10.0;
-      }
+    if (!first_failure(info) || attempt >= max_jitter_tries) break;
+    next_rung(c, info);
   }
-  if (jitter_out) memcpy(jitter_out, c->jitter.data(), sizeof(double) * m);
-  c->last_info = info;
-  if (bad) {
-    bocf_set_error("not positive definite, even with jitter.");
-    return bad;
-  }
-  if (lml_out) memcpy(lml_out, reinterpret_cast<double*>(static_cast<char*>(c->fit_pin) + ((sizeof(int) * (m + 1) + 7) / 8) * 8), sizeof(double) * m);
+  if (const int bad = end_ladder(c, info, jitter_out)) return bad;
+  if (lml_out) memcpy(lml_out, static_cast<char*>(c->fit_pin) + ioff, sizeof(double) * m);
   LAUNCHCHK();
   c->fitted = true;
   c->fits_done++;
   return 0;
 }
 
+extern "C" int bocf_fit(bocf_ctx* c, const double* X, const double* Y, int N, int d, int m, int kernel_id, const double* variance,
+                        const double* lengthscale, const double* noise, int max_jitter_tries, double* jitter_out, double* lml_out) {
+  const FitInput in{X, Y, N, d, m, kernel_id, variance, lengthscale, noise};
+  if (check_fit_input(c, "bocf_fit", in)) return -1;
+  if ((c->shard_fit && (c->comm || c->shard_fit_simulate > 0)) && !c->reuse_data && m > 1 && m % c->hyper_samples == 0)
+    return fit_sharded(c, in, max_jitter_tries, jitter_out, lml_out);
+  return fit_replicated(c, in, option_settings(c, false), max_jitter_tries, jitter_out, lml_out);
+}
+
 // yc, alpha, log-marginal and the cached posterior mean at the training inputs from host targets Y (m, N)
 static int refresh_targets(bocf_ctx* c, const double* Y, double* lml_out) {
-  const int N = c->N, Np = c->Np, m = c->m, d = c->d, nb = Np / BOCF_TILE;
-  const long strideS = (long)Np * Np;
-  std::vector<double> yc((size_t)m * Np, 0.0);
-  for (int j = 0; j < m; ++j) {
-    double s = 0.0;
-    for (int i = 0; i < N; ++i) s += Y[(long)j * N + i];
-    const double mean = s / N;
-    c->hyp[j].ymean = mean;
-    for (int i = 0; i < N; ++i) yc[(long)j * Np + i] = Y[(long)j * N + i] - mean;
-  }
+  const int Np = c->Np, m = c->m;
+  const std::vector<double> yc = centre_targets(c, Y, c->N, Np, m);
   HIPCHK(hipMemcpyAsync(c->hypd.p, c->hyp.data(), sizeof(KernHyp) * m, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(c->yc.p, yc.data(), sizeof(double) * (size_t)m * Np, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -629,38 +663,22 @@ extern "C" int bocf_lml_gradients(bocf_ctx* c, double* dvariance_out, double* dl
 
 // One hyper-parameter inference: log-marginal and its gradients at the given hyper-parameters -- the unit of work of
 // GPModel.updateModel's optimiser and HMC (gpmodel.py:115-118; hmc.py:62-66 calls it 20 times per draw).  Models with
-// N <= 128 and d <= 16 (the usual size of a BO run) take ONE fused launch per jitter attempt; anything else is
-// bocf_fit + bocf_lml_gradients.  The fused path leaves no factor behind (the context is un-fitted afterwards).
+// N <= 128 and d <= 16 (the usual size of a BO run) take ONE fused launch per jitter attempt; anything else is the replicated
+// fit (Ky^-1 wanted, never output-sharded: the gradients need the upper factor on this rank) + bocf_lml_gradients.  The fused path
+// leaves no factor behind (the context is un-fitted afterwards).
 extern "C" int bocf_infer(bocf_ctx* c, const double* X, const double* Y, int N, int d, int m, int kernel_id, const double* variance,
                           const double* lengthscale, const double* noise, int max_jitter_tries, double* jitter_out, double* lml_out,
                           double* dvariance_out, double* dlengthscale_out, double* dnoise_out) {
-  if (!c || !X || !Y || !variance || !lengthscale || !noise) return drop_kernel_ids(c, fail("bocf_infer", "null argument"));
-  const int Np = round_up(N < 1 ? 1 : N, BOCF_TILE);
-  if (!c->fused_infer || Np != BOCF_TILE || d > BOCF_INFER_MAX_D) {
-    const int sf = c->shard_fit;                         // an inference needs the upper factor on this rank: never output-sharded
-    c->shard_fit = 0;
-    c->want_kinv = 1;
-    const int rc = bocf_fit(c, X, Y, N, d, m, kernel_id, variance, lengthscale, noise, max_jitter_tries, jitter_out, lml_out);
-    c->shard_fit = sf;
-    c->want_kinv = 0;
+  const FitInput in{X, Y, N, d, m, kernel_id, variance, lengthscale, noise};
+  if (check_fit_input(c, "bocf_infer", in)) return -1;
+  if (!c->fused_infer || N > BOCF_TILE || d > BOCF_INFER_MAX_D) {
+    const int rc = fit_replicated(c, in, option_settings(c, true), max_jitter_tries, jitter_out, lml_out);
     if (rc) return rc;
     return bocf_lml_gradients(c, dvariance_out, dlengthscale_out, dnoise_out);
   }
-  if (N < 1 || d < 1 || m < 1 || m > BOCF_MAX_FITS) return drop_kernel_ids(c, fail("bocf_infer", "N, d or m out of range"));
-  if (kernel_id < 0 || kernel_id > 3) return drop_kernel_ids(c, fail("bocf_infer", "unknown kernel id"));
-  for (int j = 0; j < m; ++j) {
-    if (!(variance[j] > 0.0) || !(noise[j] >= 0.0)) return drop_kernel_ids(c, fail("bocf_infer", "variance must be > 0 and noise >= 0"));
-    for (int q = 0; q < d; ++q)
-      if (!(lengthscale[(long)j * d + q] > 0.0)) return drop_kernel_ids(c, fail("bocf_infer", "lengthscale must be > 0"));
-  }
   HIPCHK(hipSetDevice(c->device));
-  c->fitted = false;
-  c->canned = false;
-  c->have_acq = false;
-  c->r32_valid = false; c->ri8_valid = false;
-  c->N = N; c->Np = Np; c->d = d; c->m = m; c->kernel_id = kernel_id;
-  if (take_kernel_ids(c, m)) return -1;
-  const int nout = 2 + d + 2;                                // gradients, log-marginal, info
+  if (begin_model(c, in)) return -1;
+  const int Np = c->Np, nout = 2 + d + 2;                   // gradients, log-marginal, info
   if (c->X.ensure(sizeof(double) * (size_t)Np * d) || c->yc.ensure(sizeof(double) * (size_t)m * Np) || c->hypd.ensure(sizeof(KernHyp) * m))
     return -1;
   if (c->infer_out_cap < (size_t)m * nout) {
@@ -672,11 +690,10 @@ extern "C" int bocf_infer(bocf_ctx* c, const double* X, const double* Y, int N, 
   }
   double* out_dev = nullptr;
   HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&out_dev), c->infer_out, 0));
-  if (stage_data(c, X, Y, N, Np, d, m, variance, lengthscale, noise)) return -1;
+  if (stage_data(c, in, c->reuse_data != 0)) return -1;
   c->jitter.assign(m, 0.0);
   std::vector<int> info(m, 0);
-  std::vector<double> lml(m), out((size_t)m * nout);
-  int bad = 0;
+  std::vector<double> out((size_t)m * nout);
   for (int attempt = 0;; ++attempt) {                      // jitchol ladder (GPy/util/linalg.py:52-71)
     if (attempt > 0) {                                     // attempt 0: stage_data uploaded the hyper-parameters with jitter 0
       for (int j = 0; j < m; ++j) c->hyp[j].jitter = c->jitter[j] - c->test_diag_shift;
@@ -685,33 +702,112 @@ extern "C" int bocf_infer(bocf_ctx* c, const double* X, const double* Y, int N, 
     launch_infer128(c->X.as<double>(), N, d, kernel_id, c->hypd.as<KernHyp>(), c->yc.as<double>(), out_dev, m, c->stream, BOCF_KIDS(c));
     HIPCHK(hipStreamSynchronize(c->stream));
     memcpy(out.data(), c->infer_out, sizeof(double) * out.size());
-    bad = 0;
-    for (int j = 0; j < m; ++j) {
-      info[j] = (int)out[(size_t)j * nout + nout - 1];
-      lml[j] = out[(size_t)j * nout + nout - 2];
-      if (info[j] != 0 && bad == 0) bad = info[j];
-    }
-    if (!bad || attempt >= max_jitter_tries) break;
-    for (int j = 0; j < m; ++j)
-      if (info[j] != 0) {
-        const double diag_mean = c->hyp[j].variance + c->hyp[j].noise + 1e-8 - c->test_diag_shift;
-        c->jitter[j] = c->jitter[j] == 0.0 ? diag_mean * 1e-6 : c->jitter[j] * 10.0;
-      }
+    for (int j = 0; j < m; ++j) info[j] = (int)out[(size_t)j * nout + nout - 1];
+    if (!first_failure(info) || attempt >= max_jitter_tries) break;
+    next_rung(c, info);
   }
   LAUNCHCHK();
-  if (jitter_out) memcpy(jitter_out, c->jitter.data(), sizeof(double) * m);
-  c->last_info = info;
-  if (bad) {
-    bocf_set_error("not positive definite, even with jitter.");
-    return bad;
-  }
+  if (const int bad = end_ladder(c, info, jitter_out)) return bad;
   for (int j = 0; j < m; ++j) {
-    if (lml_out) lml_out[j] = lml[j];
+    if (lml_out) lml_out[j] = out[(size_t)j * nout + nout - 2];
     if (dvariance_out) dvariance_out[j] = out[(size_t)j * nout];
     if (dnoise_out) dnoise_out[j] = out[(size_t)j * nout + 1];
     if (dlengthscale_out)
       for (int q = 0; q < d; ++q) dlengthscale_out[(size_t)j * d + q] = out[(size_t)j * nout + 2 + q];
   }
+  return 0;
+}
+
+// The host arguments the two HMC chains share: theta (m, P = 2 + nls: variance, nls lengthscales, noise per output; in / out), which of
+// them are fixed, the prior, the host-drawn momenta (m, num_samples, P) and uniforms (m, num_samples), and the outputs.
+struct ChainInput {
+  const double *X, *Y;
+  int N, d, m, kernel_id;
+  double* theta; int nls; const int* fixed; double prior_a, prior_b;
+  const double *momenta, *uniforms; int num_samples, hmc_iters; double stepsize;
+  double* chains_out; int *accepted_out, *diverged_out; long long* inferences_out;
+};
+
+// The argument checks of bocf_hmc (`fused`: one workgroup per output, so also N <= 128, d <= 16, max_jitter_tries >= 0) and
+// bocf_hmc_streamed (`who`).  `flag_out` is the entry point's own required output (status_out / draws_done_out).
+static int check_chain_input(bocf_ctx* c, const char* who, const ChainInput& h, const void* flag_out, bool fused, int max_jitter_tries) {
+  if (!c || !h.X || !h.Y || !h.theta || !h.fixed || !h.momenta || !h.uniforms || !h.chains_out || !h.accepted_out || !flag_out)
+    return drop_kernel_ids(c, fail(who, "null argument"));
+  if (h.N < 1 || (fused && h.N > BOCF_TILE) || h.d < 1 || h.d > (fused ? BOCF_INFER_MAX_D : BOCF_MAX_D) || h.m < 1 || h.m > BOCF_MAX_FITS)
+    return drop_kernel_ids(c, fail(who, fused ? "N (<= 128), d (<= 16) or m out of range" : "N, d or m out of range"));
+  if (h.kernel_id < 0 || h.kernel_id > 3) return drop_kernel_ids(c, fail(who, "unknown kernel id"));
+  if (h.nls != 1 && h.nls != h.d) return drop_kernel_ids(c, fail(who, "nls must be 1 (isotropic) or d (ARD)"));
+  if (h.num_samples < 1 || h.hmc_iters < 1 || !(h.stepsize > 0.0) || !(h.prior_a > 0.0) || !(h.prior_b > 0.0) || (fused && max_jitter_tries < 0))
+    return drop_kernel_ids(c, fail(who, fused ? "num_samples, hmc_iters, stepsize, prior or max_jitter_tries out of range"
+                                              : "num_samples, hmc_iters, stepsize or prior out of range"));
+  const int P = 2 + h.nls;
+  for (int j = 0; j < h.m; ++j) {
+    int nfree = 0;
+    for (int k = 0; k < P; ++k) {
+      const double t = h.theta[(size_t)j * P + k];
+      if (!(t > 0.0) && !(k == P - 1 && t == 0.0)) return drop_kernel_ids(c, fail(who, "theta must be positive (noise >= 0)"));
+      nfree += h.fixed[(size_t)j * P + k] ? 0 : 1;
+    }
+    if (nfree < 1) return drop_kernel_ids(c, fail(who, "an output has no free parameter"));
+  }
+  return 0;
+}
+
+// The fit input at the chain's starting point: theta unpacked (one lengthscale for every input when nls = 1) into `store`.
+static FitInput chain_fit_input(const ChainInput& h, std::vector<double>& store) {
+  const int m = h.m, d = h.d, P = 2 + h.nls;
+  store.assign((size_t)m * (2 + d), 0.0);
+  double *var = store.data(), *nz = var + m, *ls = nz + m;
+  for (int j = 0; j < m; ++j) {
+    var[j] = h.theta[(size_t)j * P];
+    nz[j] = h.theta[(size_t)j * P + P - 1];
+    for (int q = 0; q < d; ++q) ls[(size_t)j * d + q] = h.theta[(size_t)j * P + 1 + (h.nls == 1 ? 0 : q)];
+  }
+  return FitInput{h.X, h.Y, h.N, d, m, h.kernel_id, var, ls, nz};
+}
+
+// One scratch block per chain: theta | momenta | uniforms | chains | stream state (doubles), inference counts (long long), fixed |
+// accepted | diverged | status | abort word + padding (ints).  The stream state (nstate doubles) and the abort word are the streamed
+// chain's, the status the fused chain's.  theta, momenta, uniforms and fixed are uploaded, chains and state zeroed; the counters are
+// the caller's.
+struct HmcBlock {
+  double *theta, *mom, *uni, *chains, *state;
+  long long* n_infer;
+  int *fixed, *accepted, *diverged, *status, *abort;
+};
+
+static int hmc_block(bocf_ctx* c, const ChainInput& h, size_t nstate, HmcBlock* b) {
+  const size_t m = h.m, nth = m * (2 + h.nls), nmom = nth * h.num_samples, nuni = m * h.num_samples;
+  if (c->hmc_buf.ensure(sizeof(double) * (nth + nmom + nuni + nmom + nstate) + sizeof(long long) * m + sizeof(int) * (nth + 3 * m + 4))) return -1;
+  b->theta = c->hmc_buf.as<double>(); b->mom = b->theta + nth; b->uni = b->mom + nmom; b->chains = b->uni + nuni; b->state = b->chains + nmom;
+  b->n_infer = reinterpret_cast<long long*>(b->state + nstate);
+  b->fixed = reinterpret_cast<int*>(b->n_infer + m); b->accepted = b->fixed + nth; b->diverged = b->accepted + m; b->status = b->diverged + m;
+  b->abort = b->status + m;
+  HIPCHK(hipMemcpyAsync(b->theta, h.theta, sizeof(double) * nth, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(b->mom, h.momenta, sizeof(double) * nmom, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(b->uni, h.uniforms, sizeof(double) * nuni, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(b->fixed, h.fixed, sizeof(int) * nth, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(b->chains, 0, sizeof(double) * (nmom + nstate), c->stream));
+  return 0;
+}
+
+// The chain's results back to the host: theta, chains, accepted, diverged, the fused chain's status (status_out), the inference count.
+static int hmc_read_back(bocf_ctx* c, const ChainInput& h, const HmcBlock& b, int* status_out) {
+  const size_t m = h.m, nth = m * (2 + h.nls), nmom = nth * h.num_samples;
+  std::vector<long long> ninf(m, 0);
+  std::vector<int> dv(m, 0);
+  HIPCHK(hipMemcpyAsync(h.theta, b.theta, sizeof(double) * nth, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(h.chains_out, b.chains, sizeof(double) * nmom, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(h.accepted_out, b.accepted, sizeof(int) * m, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(dv.data(), b.diverged, sizeof(int) * m, hipMemcpyDeviceToHost, c->stream));
+  if (status_out) HIPCHK(hipMemcpyAsync(status_out, b.status, sizeof(int) * m, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(ninf.data(), b.n_infer, sizeof(long long) * m, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  LAUNCHCHK();
+  if (h.diverged_out) memcpy(h.diverged_out, dv.data(), sizeof(int) * m);
+  long long total = 0;
+  for (size_t j = 0; j < m; ++j) total = ninf[j] > total ? ninf[j] : total;   // (the chains run side by side: one "batched inference" per step, as hyper.py counts)
+  if (h.inferences_out) *h.inferences_out = total;
   return 0;
 }
 
@@ -724,101 +820,44 @@ extern "C" int bocf_hmc(bocf_ctx* c, const double* X, const double* Y, int N, in
                         const int* fixed, double prior_a, double prior_b, const double* momenta, const double* uniforms, int num_samples,
                         int hmc_iters, double stepsize, int max_jitter_tries, int raise_on_failure, double* chains_out, int* accepted_out,
                         int* diverged_out, int* status_out, long long* inferences_out) {
-  if (!c || !X || !Y || !theta || !fixed || !momenta || !uniforms || !chains_out || !accepted_out || !status_out)
-    return drop_kernel_ids(c, fail("bocf_hmc", "null argument"));
-  if (N < 1 || N > BOCF_TILE || d < 1 || d > BOCF_INFER_MAX_D || m < 1 || m > BOCF_MAX_FITS) return drop_kernel_ids(c, fail("bocf_hmc", "N (<= 128), d (<= 16) or m out of range"));
-  if (kernel_id < 0 || kernel_id > 3) return drop_kernel_ids(c, fail("bocf_hmc", "unknown kernel id"));
-  if (nls != 1 && nls != d) return drop_kernel_ids(c, fail("bocf_hmc", "nls must be 1 (isotropic) or d (ARD)"));
-  if (num_samples < 1 || hmc_iters < 1 || !(stepsize > 0.0) || !(prior_a > 0.0) || !(prior_b > 0.0) || max_jitter_tries < 0)
-    return drop_kernel_ids(c, fail("bocf_hmc", "num_samples, hmc_iters, stepsize, prior or max_jitter_tries out of range"));
-  const int P = 2 + nls, Np = BOCF_TILE;
-  for (int j = 0; j < m; ++j) {
-    int nfree = 0;
-    for (int k = 0; k < P; ++k) {
-      const double t = theta[(size_t)j * P + k];
-      if (!(t > 0.0) && !(k == P - 1 && t == 0.0)) return drop_kernel_ids(c, fail("bocf_hmc", "theta must be positive (noise >= 0)"));
-      nfree += fixed[(size_t)j * P + k] ? 0 : 1;
-    }
-    if (nfree < 1) return drop_kernel_ids(c, fail("bocf_hmc", "an output has no free parameter"));
-  }
+  const ChainInput h{X, Y, N, d, m, kernel_id, theta, nls, fixed, prior_a, prior_b, momenta, uniforms, num_samples, hmc_iters, stepsize,
+                     chains_out, accepted_out, diverged_out, inferences_out};
+  if (check_chain_input(c, "bocf_hmc", h, status_out, true, max_jitter_tries)) return -1;
   HIPCHK(hipSetDevice(c->device));
-  c->fitted = false; c->canned = false; c->have_acq = false; c->r32_valid = false; c->ri8_valid = false;
-  c->N = N; c->Np = Np; c->d = d; c->m = m; c->kernel_id = kernel_id;
-  if (take_kernel_ids(c, m)) return -1;
+  std::vector<double> store;
+  const FitInput in = chain_fit_input(h, store);
+  if (begin_model(c, in)) return -1;
+  const int Np = c->Np;
   if (c->X.ensure(sizeof(double) * (size_t)Np * d) || c->yc.ensure(sizeof(double) * (size_t)m * Np) || c->hypd.ensure(sizeof(KernHyp) * m)) return -1;
-  {
-    std::vector<double> var(m), ls((size_t)m * d), nz(m);
-    for (int j = 0; j < m; ++j) {
-      var[j] = theta[(size_t)j * P];
-      nz[j] = theta[(size_t)j * P + P - 1];
-      for (int q = 0; q < d; ++q) ls[(size_t)j * d + q] = theta[(size_t)j * P + 1 + (nls == 1 ? 0 : q)];
-    }
-    const int reuse = c->reuse_data;
-    if (reuse && !(c->data_N == N && c->data_d == d && c->data_m == m && (int)c->hyp.size() == m)) c->reuse_data = 0;   // (first call of a data set)
-    const int rc = stage_data(c, X, Y, N, Np, d, m, var.data(), ls.data(), nz.data());
-    c->reuse_data = reuse;
-    if (rc) return -1;
-  }
-  const size_t nth = (size_t)m * P, nmom = (size_t)m * num_samples * P, nuni = (size_t)m * num_samples;
-  // one scratch block: theta | momenta | uniforms | chains (doubles), then fixed | accepted | diverged | status (ints), n_infer (long long)
-  const size_t dbl = nth + nmom + nuni + nmom, ints = nth + 3 * (size_t)m;
-  const size_t bytes = sizeof(double) * dbl + sizeof(long long) * m + sizeof(int) * ints;
-  if (c->hmc_buf.ensure(bytes)) return -1;
-  double* dth = c->hmc_buf.as<double>();
-  double* dmom = dth + nth;
-  double* duni = dmom + nmom;
-  double* dch = duni + nuni;
-  long long* dninf = reinterpret_cast<long long*>(dch + nmom);
-  int* dfix = reinterpret_cast<int*>(dninf + m);
-  int* dacc = dfix + nth;
-  int* ddiv = dacc + m;
-  int* dst = ddiv + m;
-  HIPCHK(hipMemcpyAsync(dth, theta, sizeof(double) * nth, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(dmom, momenta, sizeof(double) * nmom, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(duni, uniforms, sizeof(double) * nuni, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(dfix, fixed, sizeof(int) * nth, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(dch, 0, sizeof(double) * nmom, c->stream));
-  HIPCHK(hipMemsetAsync(dacc, 0, sizeof(int) * 3 * (size_t)m, c->stream));
+  if (stage_data(c, in, c->reuse_data && data_resident(c, in))) return -1;   // (the first call of a data set uploads it)
+  HmcBlock b;
+  if (hmc_block(c, h, 0, &b)) return -1;
+  HIPCHK(hipMemsetAsync(b.accepted, 0, sizeof(int) * 3 * (size_t)m, c->stream));   // accepted | diverged | status
   HmcArgs a{};
   a.X = c->X.as<double>(); a.N = N; a.d = d; a.yc = c->yc.as<double>();
-  a.theta = dth; a.fixed = dfix; a.P = P; a.nls = nls;
+  a.theta = b.theta; a.fixed = b.fixed; a.P = 2 + nls; a.nls = nls;
   a.prior_a = prior_a; a.prior_b = prior_b; a.prior_const = -lgamma(prior_a) + prior_a * log(prior_b);   // priors.py:271
-  a.mom = dmom; a.uni = duni; a.ns = num_samples; a.iters = hmc_iters; a.eps = stepsize;
+  a.mom = b.mom; a.uni = b.uni; a.ns = num_samples; a.iters = hmc_iters; a.eps = stepsize;
   a.max_tries = max_jitter_tries; a.raise_on_failure = raise_on_failure ? 1 : 0; a.diag_shift = c->test_diag_shift;
-  a.chains = dch; a.accepted = dacc; a.diverged = ddiv; a.status = dst; a.n_infer = dninf;
+  a.chains = b.chains; a.accepted = b.accepted; a.diverged = b.diverged; a.status = b.status; a.n_infer = b.n_infer;
   launch_hmc128(a, kernel_id, m, c->stream, BOCF_KIDS(c));
-  std::vector<long long> ninf(m, 0);
-  std::vector<int> dv(m, 0);
-  HIPCHK(hipMemcpyAsync(theta, dth, sizeof(double) * nth, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(chains_out, dch, sizeof(double) * nmom, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(accepted_out, dacc, sizeof(int) * m, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(dv.data(), ddiv, sizeof(int) * m, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(status_out, dst, sizeof(int) * m, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(ninf.data(), dninf, sizeof(long long) * m, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  LAUNCHCHK();
-  if (diverged_out) memcpy(diverged_out, dv.data(), sizeof(int) * m);
-  long long total = 0;
-  int bad = 0;
-  for (int j = 0; j < m; ++j) {
-    total = ninf[j] > total ? ninf[j] : total;            // (the chains run side by side: one "batched inference" per step, as hyper.py counts)
-    if (status_out[j] != 0) bad = 1;
-  }
-  if (inferences_out) *inferences_out = total;
-  if (bad) bocf_set_error("not positive definite, even with jitter.");
-  return bad;
+  if (hmc_read_back(c, h, b, status_out)) return -1;
+  for (int j = 0; j < m; ++j)
+    if (status_out[j] != 0) return bocf_set_error("not positive definite, even with jitter."), 1;
+  return 0;
 }
 
 // The device work of ONE inference at the hyper-parameters in c->hypd, enqueued on the context's stream without any host interaction:
-// what bocf_fit (attempt 0 of the ladder, no refinement / train mean) + bocf_lml_gradients launch.  Results: c->lml, c->gout, c->info.
-static int enqueue_inference(bocf_ctx* c, const CholPlan& plan) {
+// what the replicated fit (attempt 0 of the ladder, no refinement / train mean) + bocf_lml_gradients launch, the factorization by `plan`.
+// Results: c->lml, c->gout, c->info.
+static int enqueue_inference(bocf_ctx* c, const CholPlan& plan, bool counters_zeroed) {
   const int N = c->N, Np = c->Np, m = c->m, d = c->d;
   const long strideS = (long)Np * Np;
-  // (the inputs were scaled, the schedule counters zeroed, by the PRE launch of hmc_stream_kernel; its POST launch takes the log-marginal
-  //  and reduces the gradient partials)
+  // (the inputs were scaled, the schedule counters zeroed when counters_zeroed, by the PRE launch of hmc_stream_kernel; its POST launch
+  //  takes the log-marginal and reduces the gradient partials)
   launch_build_train_kernel(c->Xs.as<double>(), c->xs_stride, N, Np, d, c->kernel_id, c->hypd.as<KernHyp>(), c->jit.as<double>(), 1,
                             c->S.as<double>(), strideS, m, c->stream, BOCF_KIDS(c));
-  if (bocf_run_cholesky(c, &plan)) return -1;
+  if (bocf_run_cholesky(c, plan, counters_zeroed)) return -1;
   if (c->early_inverse_started) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_inv_early, 0));
   if (bocf_run_trtri(c, c->early_inverse_started != 0)) return -1;
   if (solve_alpha(c, false, false)) return -1;
@@ -835,121 +874,69 @@ extern "C" int bocf_hmc_streamed(bocf_ctx* c, const double* X, const double* Y, 
                                  const int* fixed, double prior_a, double prior_b, const double* momenta, const double* uniforms, int num_samples,
                                  int hmc_iters, double stepsize, double* chains_out, int* accepted_out, int* diverged_out, int* draws_done_out,
                                  long long* inferences_out) {
-  if (!c || !X || !Y || !theta || !fixed || !momenta || !uniforms || !chains_out || !accepted_out || !draws_done_out)
-    return drop_kernel_ids(c, fail("bocf_hmc_streamed", "null argument"));
-  if (N < 1 || d < 1 || d > BOCF_MAX_D || m < 1 || m > BOCF_MAX_FITS) return drop_kernel_ids(c, fail("bocf_hmc_streamed", "N, d or m out of range"));
-  if (kernel_id < 0 || kernel_id > 3) return drop_kernel_ids(c, fail("bocf_hmc_streamed", "unknown kernel id"));
-  if (nls != 1 && nls != d) return drop_kernel_ids(c, fail("bocf_hmc_streamed", "nls must be 1 (isotropic) or d (ARD)"));
-  if (num_samples < 1 || hmc_iters < 1 || !(stepsize > 0.0) || !(prior_a > 0.0) || !(prior_b > 0.0))
-    return drop_kernel_ids(c, fail("bocf_hmc_streamed", "num_samples, hmc_iters, stepsize or prior out of range"));
-  const int P = 2 + nls;
-  for (int j = 0; j < m; ++j) {
-    int nfree = 0;
-    for (int k = 0; k < P; ++k) {
-      const double t = theta[(size_t)j * P + k];
-      if (!(t > 0.0) && !(k == P - 1 && t == 0.0)) return drop_kernel_ids(c, fail("bocf_hmc_streamed", "theta must be positive (noise >= 0)"));
-      nfree += fixed[(size_t)j * P + k] ? 0 : 1;
-    }
-    if (nfree < 1) return drop_kernel_ids(c, fail("bocf_hmc_streamed", "an output has no free parameter"));
-  }
+  const ChainInput h{X, Y, N, d, m, kernel_id, theta, nls, fixed, prior_a, prior_b, momenta, uniforms, num_samples, hmc_iters, stepsize,
+                     chains_out, accepted_out, diverged_out, inferences_out};
+  if (check_chain_input(c, "bocf_hmc_streamed", h, draws_done_out, false, 0)) return -1;
   *draws_done_out = 0;
   if (inferences_out) *inferences_out = 0;
-  struct Unset { bocf_ctx* c; ~Unset() { c->flags_device_zeroed = 0; c->want_kinv = 0; } } unset{c};
   // ---- one ordinary inference at the starting point: stages X / Y (unless option reuse_data says they are resident), sizes every buffer,
   //      pays the one-time costs.  A start that needs jitter is the host's (draws_done = 0).
   {
-    std::vector<double> var(m), ls((size_t)m * d), nz(m);
-    for (int j = 0; j < m; ++j) {
-      var[j] = theta[(size_t)j * P];
-      nz[j] = theta[(size_t)j * P + P - 1];
-      for (int q = 0; q < d; ++q) ls[(size_t)j * d + q] = theta[(size_t)j * P + 1 + (nls == 1 ? 0 : q)];
-    }
-    const int sf = c->shard_fit, smt = c->skip_mu_train;
-    c->shard_fit = 0; c->skip_mu_train = 1; c->want_kinv = 1;
-    int rc = bocf_fit(c, X, Y, N, d, m, kernel_id, var.data(), ls.data(), nz.data(), 0, nullptr, nullptr);
+    std::vector<double> store;
+    FitSettings s = option_settings(c, true);
+    s.refine = false;                                      // (the chain reads no train mean)
+    int rc = fit_replicated(c, chain_fit_input(h, store), s, 0, nullptr, nullptr);
     if (rc == 0) rc = bocf_lml_gradients(c, nullptr, nullptr, nullptr);
-    c->shard_fit = sf; c->skip_mu_train = smt;
     if (rc < 0) return -1;
     if (rc > 0) return 0;
   }
   HIPCHK(hipSetDevice(c->device));
   c->have_acq = false;
-  const size_t nth = (size_t)m * P, nmom = (size_t)m * num_samples * P, nuni = (size_t)m * num_samples;
-  const size_t nstate = (size_t)hmc_stream_state_doubles(m);
-  // one scratch block: theta | momenta | uniforms | chains | state (doubles), n_eval (long long), fixed | accepted | diverged | abort (ints)
-  const size_t dbl = nth + nmom + nuni + nmom + nstate, ints = nth + 2 * (size_t)m + 4;
-  if (c->hmc_buf.ensure(sizeof(double) * dbl + sizeof(long long) * m + sizeof(int) * ints)) return -1;
-  double* dth = c->hmc_buf.as<double>();
-  double* dmom = dth + nth;
-  double* duni = dmom + nmom;
-  double* dch = duni + nuni;
-  double* dstate = dch + nmom;
-  long long* dninf = reinterpret_cast<long long*>(dstate + nstate);
-  int* dfix = reinterpret_cast<int*>(dninf + m);
-  int* dacc = dfix + nth;
-  int* ddiv = dacc + m;
-  int* dabort = ddiv + m;
+  HmcBlock b;
+  if (hmc_block(c, h, (size_t)hmc_stream_state_doubles(m), &b)) return -1;
   const int minus1 = -1;
-  HIPCHK(hipMemcpyAsync(dth, theta, sizeof(double) * nth, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(dmom, momenta, sizeof(double) * nmom, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(duni, uniforms, sizeof(double) * nuni, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(dfix, fixed, sizeof(int) * nth, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(dch, 0, sizeof(double) * (nmom + nstate), c->stream));
-  HIPCHK(hipMemsetAsync(dninf, 0, sizeof(long long) * m, c->stream));
-  HIPCHK(hipMemsetAsync(dacc, 0, sizeof(int) * 2 * (size_t)m, c->stream));
-  HIPCHK(hipMemcpyAsync(dabort, &minus1, sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(b.n_infer, 0, sizeof(long long) * m, c->stream));
+  HIPCHK(hipMemsetAsync(b.accepted, 0, sizeof(int) * 2 * (size_t)m, c->stream));   // accepted | diverged
+  HIPCHK(hipMemcpyAsync(b.abort, &minus1, sizeof(int), hipMemcpyHostToDevice, c->stream));
   HmcStreamArgs a{};
-  a.m = m; a.P = P; a.nls = nls; a.d = d; a.ns = num_samples; a.iters = hmc_iters;
+  a.m = m; a.P = 2 + nls; a.nls = nls; a.d = d; a.ns = num_samples; a.iters = hmc_iters;
   a.eps = stepsize; a.prior_a = prior_a; a.prior_b = prior_b; a.prior_const = -lgamma(prior_a) + prior_a * log(prior_b);   // priors.py:271
   a.diag_shift = c->test_diag_shift;
-  a.fixed = dfix; a.mom = dmom; a.uni = duni; a.state = dstate; a.chains = dch; a.accepted = dacc; a.diverged = ddiv; a.n_eval = dninf;
-  a.abort_draw = dabort; a.hyp = c->hypd.as<KernHyp>();
-  a.info = c->info.as<int>(); a.theta = dth;
+  a.fixed = b.fixed; a.mom = b.mom; a.uni = b.uni; a.state = b.state; a.chains = b.chains; a.accepted = b.accepted; a.diverged = b.diverged;
+  a.n_eval = b.n_infer; a.abort_draw = b.abort; a.hyp = c->hypd.as<KernHyp>();
+  a.info = c->info.as<int>(); a.theta = b.theta;
   a.X = c->X.as<double>(); a.Xs = c->Xs.as<double>(); a.strideXs = c->xs_stride; a.N = N; a.Np = c->Np;
   a.S = c->S.as<double>(); a.strideS = (long)c->Np * c->Np; a.alpha = c->alpha.as<double>(); a.yc = c->yc.as<double>();
   a.part = c->gpart.as<double>(); a.nblk = hypgrad_num_blocks(c->Np);
-  // every factorization of the chain runs ONE plan, made with what each of them sees (a fitted context, no redo pending); when it is the
-  // team schedule its counters are zeroed by the PRE launches instead of a memset node per step
+  // every factorization of the chain runs ONE plan, made with what each of them sees (a fitted context, no redo pending, an inference);
+  // when it is the team schedule its counters are zeroed by the PRE launches instead of a memset node per step
   CholPlan plan;
-  if (bocf_plan_cholesky(c, &plan)) return -1;
-  a.flags = nullptr; a.flag_words = 0;
+  if (bocf_plan_cholesky(c, true, &plan)) return -1;
   a.sched_err = plan.flag_ints > 0 ? c->chol_flags.as<int>() + plan.err_off : nullptr;
   if (plan.schedule == CHOL_TEAM_WHOLE) {
     a.flags = c->chol_flags.as<int>(); a.flag_words = chol_team_flag_words(c->Np / BOCF_TILE);
-    c->flags_device_zeroed = 1;
   }
+  const bool counters_zeroed = a.flags != nullptr;
   launch_hmc_stream(a, HS_INIT, 0, 0, c->stream);
-  if (enqueue_inference(c, plan)) return -1;
+  if (enqueue_inference(c, plan, counters_zeroed)) return -1;
   launch_hmc_stream(a, HS_EVAL0, 0, 0, c->stream);
   const int check_every = 8;                               // draws between two looks at the abort word (a sync each)
   int aborted = -1;
   for (int i = 0; i < num_samples && aborted < 0; ++i) {
     for (int it = 0; it < hmc_iters; ++it) {
       launch_hmc_stream(a, HS_PRE, i, it, c->stream);
-      if (enqueue_inference(c, plan)) return -1;
+      if (enqueue_inference(c, plan, counters_zeroed)) return -1;
       launch_hmc_stream(a, HS_POST, i, it, c->stream);
     }
     if ((i + 1) % check_every == 0 || i + 1 == num_samples) {
-      HIPCHK(hipMemcpyAsync(&aborted, dabort, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipMemcpyAsync(&aborted, b.abort, sizeof(int), hipMemcpyDeviceToHost, c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
     }
   }
   launch_hmc_stream(a, HS_FINISH, 0, 0, c->stream);
-  std::vector<long long> ninf(m, 0);
-  std::vector<int> dv(m, 0);
-  HIPCHK(hipMemcpyAsync(theta, dth, sizeof(double) * nth, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(chains_out, dch, sizeof(double) * nmom, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(accepted_out, dacc, sizeof(int) * m, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(dv.data(), ddiv, sizeof(int) * m, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(ninf.data(), dninf, sizeof(long long) * m, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  LAUNCHCHK();
+  if (hmc_read_back(c, h, b, nullptr)) return -1;
   c->chol_flags_used = 0;
   c->fitted = false;                                       // the factor on the device belongs to the chain's last trajectory point
-  if (diverged_out) memcpy(diverged_out, dv.data(), sizeof(int) * m);
-  long long total = 0;
-  for (int j = 0; j < m; ++j) total = ninf[j] > total ? ninf[j] : total;
-  if (inferences_out) *inferences_out = total;
   *draws_done_out = aborted >= 0 ? aborted : num_samples;
   return 0;
 }
