@@ -330,7 +330,7 @@ __global__ __launch_bounds__(NT) void topk_stream_kernel(const double* __restric
     long long bi = NONE;
     for (long long e = lo + threadIdx.x; e < hi; e += NT) {
       double v = vals[e];
-      if (!(v == v)) v = -INFINITY;                        // NaN sorts last
+      if (!(v == v)) v = -INFINITY;                        // NaN ranks as -inf (tied with -inf, by index) and is reported as -inf
       const long long id = idxs ? idxs[e] : e;
       if (id < 0) continue;                                // empty slot of a previous stage
       const bool worse_than_prev = v < pv || (v == pv && id > pi);
@@ -416,7 +416,7 @@ __global__ __launch_bounds__(256) void topk_wave_kernel(const double* __restrict
   for (int e = 0; e < E; ++e) {
     const long long pos = lo + threadIdx.x + 256 * e;
     double v = pos < hi ? vals[pos] : -INFINITY;
-    if (!(v == v)) v = -INFINITY;                          // NaN sorts last
+    if (!(v == v)) v = -INFINITY;                          // NaN ranks as -inf (tied with -inf, by index) and is reported as -inf
     cv[e] = v;
     ci[e] = pos < hi ? (idxs ? idxs[pos] : pos) : -1;      // id < 0: empty slot (of a previous stage, or past the end)
   }

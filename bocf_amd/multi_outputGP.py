@@ -817,7 +817,9 @@ class multi_outputGP(object):
 
     def select_topk(self, k):
         """(indices, values) of the k best candidates of the last acquisition call -- the
-        np.argsort(-acq)[:k] of anchor_points_generator.py:61, ties to the lowest index."""
+        np.argsort(-acq)[:k] of anchor_points_generator.py:61, ties to the lowest index.  A NaN
+        value ranks as -inf (after every number, tied with -inf by index) and is reported as -inf.
+        With fewer than k candidates, all of them are returned."""
         idx = np.empty(k, dtype=np.int64)
         val = np.empty(k)
         _ffi.check(_ffi.load().bocf_select_topk(self._context().handle, k, idx.ctypes.data_as(_ffi._c_ll_p), _ffi.dptr(val)),
