@@ -16,7 +16,7 @@ import time
 
 import numpy as np
 
-from .acquisition_optimizer import ContextManager
+from .acquisition_optimizer import ContextManager, _bounds_of, samples_multidimensional_uniform
 from .recommend import current_marginal_argmaxes
 
 
@@ -32,12 +32,68 @@ class Sequential(object):
         return x
 
 
+class CompositeThompsonBatch(object):
+    """q suggestions per iteration by Thompson sampling on the composite objective.  The first point is acquisition.optimize's, as in
+    Sequential (batch_size = 1 is Sequential).  Each of the q - 1 others is the argmax over a random candidate design of
+    U(theta_s, f_s(c)), with f_s a joint posterior sample of all outputs on the design and theta_s a draw of the utility parameter.
+    Draws from np.random, in this order: the design (samples_multidimensional_uniform, one np.random.uniform per dimension), theta for
+    all paths (utility.parameter_dist.sample(q - 1)), then the normals Z (m, n_candidates, paths of h) of every hyper-sample h used, in
+    increasing h.  Path s uses hyper-sample s mod min(10, number_of_hyps_samples()).  Path s takes its best candidate not taken by an
+    earlier path of the batch (model.thompson_topk gives each path its top q).  (GPyOpt's ThompsonBatch samples each output's marginal
+    and assumes a single-output model; this is a different method, hence the different name.)"""
+
+    def __init__(self, acquisition, batch_size, n_candidates=4096):
+        if int(batch_size) < 1:
+            raise ValueError("batch_size must be >= 1")
+        if int(batch_size) > int(n_candidates) or int(batch_size) > 64:
+            raise ValueError("batch_size must be <= min(n_candidates, 64)")
+        self.acquisition = acquisition
+        self.batch_size = int(batch_size)
+        self.n_candidates = int(n_candidates)
+
+    def compute_batch(self, duplicate_manager=None, context_manager=None, x_baseline=None):
+        x0, _ = self.acquisition.optimize(x_baseline=x_baseline)
+        x0 = np.atleast_2d(x0)
+        q = self.batch_size
+        if q == 1:
+            return x0
+        model, utility = self.acquisition.model, self.acquisition.utility
+        P = q - 1
+        Xc = samples_multidimensional_uniform(_bounds_of(self.acquisition.space), self.n_candidates)
+        thetas = np.asarray(utility.parameter_dist.sample(P), dtype=float).reshape(P, -1)
+        n_h = min(10, model.number_of_hyps_samples())
+        groups = np.arange(P) % n_h
+        Z = {h: np.random.normal(size=(model.output_dim, self.n_candidates, int(np.sum(groups == h)))) for h in sorted(set(groups.tolist()))}
+        idx, _ = model.thompson_topk(Xc, thetas, groups, Z, utility, q)
+        return np.vstack((x0, Xc[distinct_picks(idx)]))
+
+
+def distinct_picks(idx):
+    """Row s of idx ranks path s's candidates; path s takes its first candidate that no earlier path took."""
+    taken = []
+    for row in np.asarray(idx):
+        pick = next((int(i) for i in row if int(i) >= 0 and int(i) not in taken), None)
+        if pick is None:
+            raise RuntimeError("a Thompson path found no candidate left untaken in its top %d" % len(row))
+        taken.append(pick)
+    return np.asarray(taken, dtype=int)
+
+
 class _ConstantCost(object):
     """GPyOpt's CostModel(None): every evaluation costs the same; nothing to update."""
     cost_type = "Constant cost"
 
     def update_cost_model(self, x, cost_x):
         pass
+
+
+def _repeats(x, previous):
+    """The suggestion repeats the previous batch: for one row, equal to it (broadcast against previous, as the reference compares);
+    for q rows, the same shape and every entry equal."""
+    x, previous = np.asarray(x), np.asarray(previous)
+    if x.ndim == 2 and x.shape[0] == 1:
+        return bool(np.all(x == previous))
+    return x.shape == previous.shape and bool(np.all(x == previous))
 
 
 def _zip(space, X):
@@ -178,7 +234,7 @@ class CBO(object):
     def _one_iteration(self, parallel):
         previous = self.suggested_sample
         x = self.compute_next_evaluations()
-        self.suggested_sample = self._perturb(x) if np.all(x == previous) else x
+        self.suggested_sample = self._perturb(x) if _repeats(x, previous) else x
         try:
             # the reference calls update_Z_samples() without its required argument: the TypeError is swallowed, nothing is drawn
             self.acquisition.update_Z_samples()

@@ -178,7 +178,16 @@ struct bocf_ctx {
   void* comm = nullptr;      // ncclComm_t
   int world = 1, rank = 0;
   DevBuf pack, gidx, gval;
+  // ---- joint posterior / composite Thompson sampling (capi_thompson.hip): buffers of their own, the predict and acquisition state is left
+  // as it was.  The factorization of Sigma runs on a helper context (its S, E, ET, info, schedule state), created on first use.
+  bocf_ctx* ts_helper = nullptr;
+  DevBuf ts_X, ts_K, ts_V, ts_mp, ts_mu, ts_Z, ts_jit, ts_u, ts_theta, ts_params, ts_out;
+  std::vector<DevBuf> ts_F;  // resident samples of hyper-sample h: (m / H, C, ts_S[h]) -- ts_S[h] = 0: none
+  std::vector<int> ts_S;
 };
+
+// the resident Thompson samples belong to one posterior and one candidate set: dropped by every fit, data change and candidate upload
+void bocf_thompson_drop(bocf_ctx* c);
 
 
 // HIP-event bracket of a named phase on the context's stream (only with option "profile" = 1; otherwise free)

@@ -347,3 +347,20 @@ int topk_num_blocks(int C);
 // multi-GPU selection: pack the k local winners (+ lo) into a 2 * world * k buffer of doubles; merge the gathered buffer
 void launch_pack_topk(const long long* idx, const double* val, int k, long long lo, int world, int rank, double* pack, hipStream_t s);
 void launch_merge_packed(const double* pack, int k, int world, long long* gidx, double* gval, long long* out_idx, double* out_val, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------
+// joint posterior and composite Thompson sampling (thompson.hip)
+// ---------------------------------------------------------------------------------------
+// out[j][r][c] = k_j(x1_r, x2_c) - sum_{kk < K} V1[j][kk][r] V2[j][kk][c]  (V k-major, K a multiple of 16, ld1 / ld2 / ldo multiples of 128 covering
+// n1 / n2).  sym: X1 = X2, tiles on / above the diagonal only, padded diagonal 1, jitter[j] (optional) added to the valid diagonal.
+void launch_post_cov(const double* V1, long ld1, long strideV1, const double* V2, long ld2, long strideV2, const double* X1, int n1, const double* X2,
+                     int n2, int d, int K, int kernel_id, const int* kids, const KernHyp* hyp, const double* jitter, int sym, double* out, long ldo,
+                     long strideO, int m, hipStream_t s);
+// mode 0: mean[j] = mean of the first n diagonal entries of S_j; mode 1: those entries += jit[j]
+void launch_post_diag(double* S, long ld, long strideS, int n, int mode, double* mean, const double* jit, int m, hipStream_t s);
+// F[j][c][s] = mu[j][c] + sum_{k <= c} U[j][k][c] Z[j][k][s]   (Z, F: (m, C, S) contiguous, S <= 256)
+void launch_post_sample(const double* U, long ldu, long strideU, const double* Z, const double* mu, long ldmu, int C, int S, double* F, int m,
+                        hipStream_t s);
+// u[s][c] = U(theta_s, F[:, c, s]) (utility_dev.h) for one sample block F (m, C, S)
+void launch_thompson_util(const double* F, int m, int C, int S, int util_kind, const double* theta, int theta_dim, const double* params, double* u,
+                          long ldu, hipStream_t s);

@@ -91,6 +91,9 @@ extern "C" void bocf_destroy(bocf_ctx* c) {
   (void)bocf_comm_destroy(c);
   if (c->shard_helper) bocf_destroy(c->shard_helper);
   c->shard_helper = nullptr;
+  if (c->ts_helper) bocf_destroy(c->ts_helper);
+  c->ts_helper = nullptr;
+  for (DevBuf& b : c->ts_F) b.release();
   drop_events(c);
   drop_phases(c);
   if (c->pin_in) (void)hipHostFree(c->pin_in);
@@ -103,7 +106,8 @@ extern "C" void bocf_destroy(bocf_ctx* c) {
   DevBuf* bufs[] = {&c->R32, &c->Ri8, &c->Ri8e, &c->Ki8, &c->Ki8e, &c->X, &c->Xs, &c->S, &c->R, &c->RT, &c->E, &c->ET, &c->T, &c->yc, &c->tvec, &c->alpha, &c->lml, &c->jit, &c->hypd,
                     &c->info, &c->mu_train, &c->rvec, &c->dvec, &c->hmc_buf, &c->Xc, &c->Kstar, &c->meanpart, &c->sumsq, &c->mean, &c->var, &c->acq, &c->Vbuf, &c->dmean, &c->dvar, &c->dacq, &c->Vs, &c->Ws, &c->theta,
                     &c->prob, &c->best, &c->params, &c->Wt, &c->blk_idx, &c->blk_val, &c->out_idx, &c->out_val, &c->gpart, &c->gout, &c->pack, &c->gidx,
-                    &c->gval, &c->shard_meta, &c->chol_flags, &c->eu_theta, &c->eu_rows, &c->eu_Z, &c->eu_val, &c->eu_grad};
+                    &c->gval, &c->shard_meta, &c->chol_flags, &c->eu_theta, &c->eu_rows, &c->eu_Z, &c->eu_val, &c->eu_grad,
+                    &c->ts_X, &c->ts_K, &c->ts_V, &c->ts_mp, &c->ts_mu, &c->ts_Z, &c->ts_jit, &c->ts_u, &c->ts_theta, &c->ts_params, &c->ts_out};
   for (DevBuf* b : bufs) b->release();
   if (c->infer_out) (void)hipHostFree(c->infer_out);
   for (hipEvent_t ev : c->ev_parts) (void)hipEventDestroy(ev);
@@ -249,6 +253,7 @@ extern "C" int bocf_set_posterior(bocf_ctx* c, int m, int C, int N, const double
   c->mu_epoch++;
   HIPCHK(hipStreamSynchronize(c->stream));
   c->m = m; c->N = N; c->Np = round_up(N, BOCF_TILE); c->d = 1; c->C = C; c->pred_cap = cap;
+  bocf_thompson_drop(c);
   c->fitted = true;
   c->canned = true;
   c->have_acq = false;
@@ -279,6 +284,7 @@ extern "C" int bocf_set_candidates(bocf_ctx* c, const double* Xc, int C) {
   if (C < 0 || (C > 0 && !Xc)) return fail("bocf_set_candidates", "bad candidate batch");
   HIPCHK(hipSetDevice(c->device));
   c->have_acq = false;
+  bocf_thompson_drop(c);
   c->C = C;
   if (C == 0) return 0;
   if (c->Xc.ensure(sizeof(double) * (size_t)C * c->d)) return -1;

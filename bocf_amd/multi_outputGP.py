@@ -130,6 +130,8 @@ class multi_outputGP(object):
         self.device_hmc = True                  # N <= 128, d <= 16: the whole HMC chain in one device launch (bocf_hmc); False = lockstep host loop
         self._H = 1 if fixed_hyps else int(n_samples)     # hyper-samples resident on the device
         self._current_h = 0                                # set_hyperparameters(h)
+        self.sample_jitter_tries = 10                      # rungs of the jitter ladder of the joint posterior samples
+        self.last_sample_jitter = None                     # the jitter per output of the last posterior_samples_f / thompson_topk draw
         self._sampler_outputs = None                       # per output: parameter state of GPModel.model
         self._Ymat = None                                  # (m, N) targets, cached for the inferences of one update
         self._ibuf = None                                  # argument block of bocf_infer (arrays + ctypes pointers)
@@ -581,9 +583,86 @@ class multi_outputGP(object):
 
     partial_precomputation_for_covariance = partial_precomputation_for_covariance_gradient = _off_path
     partial_precomputation_for_variance_conditioned_on_next_point = posterior_variance_conditioned_on_next_point = _off_path
-    posterior_variance_gradient_conditioned_on_next_point = posterior_covariance_between_points = _off_path
+    posterior_variance_gradient_conditioned_on_next_point = _off_path
     posterior_covariance_between_points_partially_precomputed = posterior_covariance_gradient = _off_path
     posterior_covariance_gradient_partially_precomputed = _off_path
+
+    # ---- joint posterior and composite Thompson sampling ------------------------------------------------------------------------
+    def _group(self):
+        """Device group of the current hyper-sample (bocf_posterior_cov / bocf_posterior_samples)."""
+        return self._current_h if self._H > 1 else 0
+
+    def posterior_covariance_between_points(self, X1, X2):
+        """Noiseless, unclipped posterior covariance between X1 (n1, d) and X2 (n2, d) for the current hyper-sample
+        (multi_outputGP.py:257-266 -> gp.py:576-583 -> posterior.py:104-125): k(X1, X2) - k(X1, X) Ky^-1 k(X, X2).  Returns (m, n1, n2)."""
+        self._ensure_fitted()
+        X1, X2 = _ffi.f64(np.atleast_2d(X1)), _ffi.f64(np.atleast_2d(X2))
+        d = self._X.shape[1]
+        if X1.shape[1] != d or X2.shape[1] != d:
+            raise ValueError("X1 and X2 must be (n, %d)" % d)
+        out = np.empty((self.output_dim, X1.shape[0], X2.shape[0]))
+        _ffi.check(_ffi.load().bocf_posterior_cov(self._context().handle, _ffi.dptr(X1), X1.shape[0], _ffi.dptr(X2), X2.shape[0], self._group(),
+                                                  _ffi.dptr(out)), "bocf_posterior_cov")
+        return out
+
+    def _posterior_samples(self, group, Z, keep_out=True):
+        """Joint samples at the resident candidates for device group `group` from Z (M_g, C, S); returns (samples or None, jitter (M_g,))."""
+        Z = _ffi.f64(Z)
+        M = Z.shape[0]
+        out = np.empty(Z.shape) if keep_out else None
+        jit = np.empty(M)
+        rc = _ffi.load().bocf_posterior_samples(self._context().handle, int(group), _ffi.dptr(Z), Z.shape[2], self.sample_jitter_tries,
+                                                _ffi.dptr(out), _ffi.dptr(jit))
+        _ffi.check(rc, "bocf_posterior_samples")
+        self.last_sample_jitter = jit
+        if rc > 0:
+            raise np.linalg.LinAlgError("posterior covariance of output %d not positive definite, even with jitter %g" % (rc - 1, jit[rc - 1]))
+        return out, jit
+
+    def posterior_samples_f(self, X, size=10, Z=None):
+        """Joint samples of the latent outputs at X (n, d) for the current hyper-sample, GPy's fsim layout (gp.py:794-828): (m, n, size).
+        f = mu + L Z with L the Cholesky factor of the noiseless posterior covariance + jitter I (jitter ladder from 1e-8 mean(diag),
+        the jitter used is kept in last_sample_jitter).  Z defaults to np.random.normal(size=(m, n, size)).  GPy draws with
+        np.random.multivariate_normal, which factors by SVD: seeded draws differ from GPy's, with the same distribution."""
+        self._ensure_fitted()
+        X = np.atleast_2d(X)
+        if Z is None:
+            Z = np.random.normal(size=(self.output_dim, X.shape[0], int(size)))
+        Z = _ffi.f64(Z)
+        if Z.shape[:2] != (self.output_dim, X.shape[0]):
+            raise ValueError("Z must be (output_dim, n, size)")
+        self._set_candidates(X)
+        return self._posterior_samples(self._group(), Z)[0]
+
+    def thompson_topk(self, X, thetas, path_groups, Z, utility, k):
+        """Composite Thompson sampling on the candidate set X (C, d): path s draws a joint sample f_s of all outputs from hyper-sample
+        path_groups[s] with the normals of Z[h] (dict: hyper-sample -> (m, C, paths of h in path order)) and ranks the candidates by
+        U(thetas[s], f_s(c)).  One device sampling call per hyper-sample used, one selection call.  Returns (idx (P, k), val (P, k)) in
+        path order, value descending, ties to the lowest index."""
+        self._ensure_fitted()
+        thetas = _ffi.f64(np.asarray(thetas, dtype=float).reshape(len(path_groups), -1))
+        path_groups = np.asarray(path_groups, dtype=int)
+        P = path_groups.size
+        dev = path_groups if self._H > 1 else np.zeros(P, dtype=int)
+        kind = utility.device_kind(self.output_dim)
+        params = utility.device_params
+        self._set_candidates(X)
+        order = []
+        for g in sorted(set(dev.tolist())):
+            hs = sorted(set(path_groups[dev == g].tolist()))          # (fixed hyper-parameters: the draws of every h feed group 0)
+            Zg = np.concatenate([Z[h] for h in hs], axis=2)
+            self._posterior_samples(g, Zg, keep_out=False)
+            order += [s for h in hs for s in np.flatnonzero(path_groups == h)]
+        order = np.asarray(order, dtype=int)
+        th = _ffi.f64(thetas[order])
+        pa = None if params is None else _ffi.f64(np.atleast_1d(params))
+        idx = np.empty((P, k), dtype=np.int64)
+        val = np.empty((P, k))
+        _ffi.check(_ffi.load().bocf_thompson_select(self._context().handle, kind, _ffi.dptr(pa), 0 if pa is None else pa.size, _ffi.dptr(th), th.shape[1],
+                                                    int(k), idx.ctypes.data_as(_ffi._c_ll_p), _ffi.dptr(val)), "bocf_thompson_select")
+        out_idx, out_val = np.empty_like(idx), np.empty_like(val)
+        out_idx[order], out_val[order] = idx, val
+        return out_idx, out_val
 
     def set_hyperparameters2(self, hyperparameters):
         """multi_outputGP.py:118-120: per-output hyper-sample indices; the device keeps hyper-samples aligned across

@@ -239,6 +239,31 @@ int bocf_predict(bocf_ctx* ctx, int flags, double* mean_out, double* var_out);
  * matrix is never formed (one extra solve w = R (R^T k(X, x_0)) and a mean-shaped pass over the candidates). */
 int bocf_predict_cov_column(bocf_ctx* ctx, int flags, double* cov0_out);
 
+/* Joint posterior over point sets and composite Thompson sampling.  All three are local to the context: they issue no collective (a
+ * multi-rank run calls them on one rank's context; sampling across candidate shards would need the cross-shard covariance).  They work on
+ * a fitted model (bocf_fit / bocf_infer; not a bocf_set_posterior one) and leave the predict and acquisition state as it was.
+ * `group` = h selects hyper-sample h's outputs [h m, (h + 1) m) of the m = outputs / hyper_samples per sample, -1 all of them; M_g is
+ * the number of outputs selected.  The covariance of M_g padded C x C matrices (M_g Cp^2 8 bytes, Cp = C rounded up to 128) must fit in
+ * option "workspace_mb", else the call fails.  Every failure returns < 0 with bocf_last_error() set; the context stays usable.
+ *
+ * bocf_posterior_cov: the noiseless, unclipped posterior covariance (posterior.py:104-125, gp.py:576-583)
+ *   cov_out[j][a][b] = k_j(x1_a, x2_b) - k_j(x1_a, X) Ky_j^-1 k_j(X, x2_b),   (M_g, n1, n2), X1 (n1, d), X2 (n2, d).
+ * bocf_posterior_samples: joint samples of the latent outputs at the resident candidates (bocf_set_candidates, C of them):
+ *   F_j = mu_j + L_j Z_j, L_j L_j^T = Sigma_j + jitter_j I, Sigma_j the candidates' covariance above and mu_j the posterior mean
+ *   (target mean included).  Z (M_g, C, S) standard normals from the host, 1 <= S <= 256; samples_out (M_g, C, S) or NULL (they stay on
+ *   the device for bocf_thompson_select); jitter_out (M_g) the jitter used.  Jitter ladder per output: rung 0 = 1e-8 max(mean(diag
+ *   Sigma_j), 1e-10), ten times the last per further rung, at most max(1, max_jitter_tries) rungs.  Returns 0, or j + 1 > 0 for the first
+ *   output j that stayed indefinite (the samples of that call are then not kept).  The samples replace the resident ones of the
+ *   hyper-samples selected (group -1: all of them); a fit, a data change or a new candidate set drops them all.
+ * bocf_thompson_select: for every resident sample path p -- hyper-samples in increasing order, then the path index within that
+ *   hyper-sample's block -- the k best candidates of u(p, c) = U(theta_p, F[:, c, p]) (the device utility util_kind with util_params, as
+ *   the acquisitions evaluate it): value descending, ties to the lowest index.  theta (P, theta_dim), one row per path; idx_out and
+ *   val_out (P, k); 1 <= k <= min(C, 64). */
+int bocf_posterior_cov(bocf_ctx* ctx, const double* X1, int n1, const double* X2, int n2, int group, double* cov_out);
+int bocf_posterior_samples(bocf_ctx* ctx, int group, const double* Z, int S, int max_jitter_tries, double* samples_out, double* jitter_out);
+int bocf_thompson_select(bocf_ctx* ctx, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim, int k,
+                         long long* idx_out, double* val_out);
+
 /* Input gradients of the posterior at the resident candidates, (m,C,d) each.  Replaces
  * multi_outputGP.posterior_mean_gradient / posterior_variance_gradient (multi_outputGP.py:284-306) ->
  * GP.posterior_mean_gradient / posterior_variance_gradient (GPy/core/gp.py:438-490) -> kern.gradients_X
