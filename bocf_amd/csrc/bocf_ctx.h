@@ -2,6 +2,7 @@
 #pragma once
 #include "bocf_internal.h"
 #include "chol_plan.h"
+#include "predict_plan.h"
 #include "../../include/bocf_hip.h"
 
 #include <map>
@@ -44,6 +45,8 @@ static inline int nsplit_for(int Np, int Cpad, int m) {
 
 
 
+static_assert(PLAN_TILE == BOCF_TILE && PLAN_SMALL_N == BOCF_SMALL_N && PLAN_I8_SLICES == BOCF_I8_SLICES, "predict_plan.h mirrors bocf_internal.h");
+
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
@@ -68,7 +71,6 @@ struct DevBuf {
 struct bocf_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
-  hipStream_t stream2 = nullptr;   // cross-kernel stream (overlaps the VALU/HBM-bound K* build with the MFMA-bound GEMM)
   // small batches (the single points and 16-point groups of the acquisition optimiser): candidates go up and results come back through pinned
   // staging buffers -- asynchronous copies, ONE stream synchronisation per call instead of one per pageable copy
   void* pin_in = nullptr; void* pin_out = nullptr;
@@ -76,8 +78,6 @@ struct bocf_ctx {
   hipEvent_t ev_pin = nullptr;     // the upload out of pin_in has completed
   void* fit_pin = nullptr; size_t fit_pin_cap = 0;     // status words + log-marginal of a fit
   void* up_pin = nullptr; size_t up_pin_cap = 0, arena_used = 0;   // pinned arena of a fit's host-to-device copies (X, hyper-parameters, targets, jitter)
-  hipEvent_t ev_start = nullptr;
-  std::vector<hipEvent_t> ev_parts;
   std::vector<hipEvent_t> ev_chol;  // lookahead Cholesky: events per panel
   // Reserved-CU lookahead (run_cholesky): the serial chain of diagonal-block factorizations runs on a stream whose CU mask
   // holds `res_cus` compute units that NO other stream of the factorization may use (the trailing updates run on streams
@@ -112,7 +112,6 @@ struct bocf_ctx {
   DevBuf hmc_buf;            // bocf_hmc: parameters, momenta, uniforms, chains, counters
   double* infer_out = nullptr;    // host-mapped result block of the fused inference (the kernel writes it over PCIe: no D2H copy)
   size_t infer_out_cap = 0;
-  int overlap = 0;                 // measured: no gain (the K* build slows the co-running GEMM by as much as it hides)
   // ---- fit state
   bool fitted = false;
   bool canned = false;       // bocf_set_posterior: mean / var / train mean were given by the host (acquisition kernels only)
@@ -212,4 +211,25 @@ struct PhaseTimer {
     e0 = nullptr;
   }
   ~PhaseTimer() { stop(); }
+};
+
+// HIP-event bracket of the dominant kernel of a predict pass (option "profile" = 1; otherwise free): bocf_profile_read sums its time,
+// counts it and adds the pass's m N^2 n flops
+struct KernelTimer {
+  bocf_ctx* c;
+  double flops;
+  hipEvent_t e0 = nullptr;
+  KernelTimer(bocf_ctx* ctx, int ncols) : c(ctx), flops((double)ctx->m * (double)ctx->N * (double)ctx->N * (double)ncols) {
+    if (!c->profile) return;
+    if (hipEventCreate(&e0) != hipSuccess) { e0 = nullptr; return; }
+    (void)hipEventRecord(e0, c->stream);
+  }
+  ~KernelTimer() {
+    if (!e0) return;
+    hipEvent_t e1 = nullptr;
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return; }
+    (void)hipEventRecord(e1, c->stream);
+    c->events.emplace_back(e0, e1);
+    c->prof_flops += flops;
+  }
 };

@@ -7,7 +7,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <utility>
 #include <string>
 #include <vector>
 
@@ -50,19 +49,13 @@ extern "C" int bocf_create(int device, bocf_ctx** out) {
     delete c;
     return fail("hipStreamCreate", hipGetErrorString(e));
   }
-  {
-    int lo_prio = 0, hi_prio = 0;   // the second stream carries the latency-critical side chains: highest priority
-    (void)hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio);
-    e = hipStreamCreateWithPriority(&c->stream2, hipStreamDefault, hi_prio);
-  }
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_start, hipEventDisableTiming);
   hipDeviceProp_t prop;
-  if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
-  if (e == hipSuccess) c->ncu = prop.multiProcessorCount;
+  e = hipGetDeviceProperties(&prop, device);
   if (e != hipSuccess) {
     delete c;
-    return fail("hipStreamCreate", hipGetErrorString(e));
+    return fail("hipGetDeviceProperties", hipGetErrorString(e));
   }
+  c->ncu = prop.multiProcessorCount;
   *out = c;
   return 0;
 }
@@ -110,14 +103,11 @@ extern "C" void bocf_destroy(bocf_ctx* c) {
                     &c->ts_X, &c->ts_K, &c->ts_V, &c->ts_mp, &c->ts_mu, &c->ts_Z, &c->ts_jit, &c->ts_u, &c->ts_theta, &c->ts_params, &c->ts_out};
   for (DevBuf* b : bufs) b->release();
   if (c->infer_out) (void)hipHostFree(c->infer_out);
-  for (hipEvent_t ev : c->ev_parts) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : c->ev_chol) (void)hipEventDestroy(ev);
-  if (c->ev_start) (void)hipEventDestroy(c->ev_start);
   for (hipStream_t st : {c->s_res, c->s_hi, c->s_bulk, c->s_inv})
     if (st) (void)hipStreamDestroy(st);
   if (c->ev_half) (void)hipEventDestroy(c->ev_half);
   if (c->ev_inv_early) (void)hipEventDestroy(c->ev_inv_early);
-  if (c->stream2) (void)hipStreamDestroy(c->stream2);
   (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -170,7 +160,6 @@ static const OptDesc g_options[] = {
     {"shard_fit", 0, 1, 0, [](bocf_ctx* c, long long v) { c->shard_fit = v != 0; }, nullptr, "output-sharded fit over the communicator"},
     {"trsm_wave", 0, 1, 0, [](bocf_ctx* c, long long v) { c->chol.trsm_wave = v != 0; }, nullptr, "row solves through the wave-level single-tile kernel"},
     {"overlap_inverse", -1, 1, 0, [](bocf_ctx* c, long long v) { c->chol.overlap_inverse = (int)v; }, nullptr, "early part of the inverse underneath the factorization (-1 = by size)"},
-    {"overlap", 0, 1, 0, [](bocf_ctx* c, long long v) { c->overlap = v != 0; }, nullptr, "K* build on a second stream"},
     {"small_path", 0, 1, 0, [](bocf_ctx* c, long long v) { c->small_path = v != 0; }, nullptr, "GEMV-shaped path for <= 16 candidates"},
     {"prefetch1", 0, 1, 0, [](bocf_ctx* c, long long v) { c->prefetch1 = v != 0; }, nullptr, "one-tile-deep staging in the 128-row variance kernel"},
     {"swizzle", -1, 258, 0, [](bocf_ctx* c, long long v) { c->swizzle = (int)v; }, opt_swizzle_ok, "variance-GEMM tiling: -1 by size, 0 128-row tiles, 258 256-row tiles (probes build: also 1, 100..163, 256, 257)"},
@@ -303,245 +292,181 @@ extern "C" int bocf_set_candidates(bocf_ctx* c, const double* Xc, int C) {
   return 0;
 }
 
-// mean / var of all resident candidates into c->mean / c->var (m, pred_cap)
-static int run_predict(bocf_ctx* c, int flags, bool need_var, bool need_grad = false) {
-  const int N = c->N, Np = c->Np, m = c->m, d = c->d, C = c->C;
+// One pass of run_predict: candidates [c0, c0 + Cn) of the resident batch, their K* and partial sums in the first Cpad columns of the workspace
+struct PredictPass {
+  const PredictPlan& p;
+  const double* w;           // mean weights: alpha, or those bocf_predict_cov_column hands over
+  int flags;                 // BOCF_ADD_NOISE / BOCF_CLIP of the variances
+  bool need_grad;
+  int c0, Cn, Cpad;
+};
+
+static int small_width(int Cn) {                             // the small path's columns: the next power of two
+  int nc = 1;
+  while (nc < Cn) nc *= 2;
+  return nc;
+}
+
+// K* of the pass (not for means only) and the partial means per 128-row block (hi and lo planes); for means only, the means themselves
+static void predict_cross(bocf_ctx* c, const PredictPass& s) {
+  const PredictPlan& p = s.p;
+  double* mp = c->meanpart.as<double>();
+  PhaseTimer t(c, "cross");
+  if (p.kind == PRED_SMALL)                                   // (the matrix-pipe form of the small path)
+    launch_cross_small(c->Xs.as<double>(), c->xs_stride, c->N, c->Np, c->d, c->kernel_id, c->hypd.as<KernHyp>(), c->Xc.as<double>(), s.c0, s.Cn,
+                       small_width(s.Cn), s.w, c->Kstar.as<double>(), s.Cpad, (long)c->Np * s.Cpad, mp, mp + p.mean_plane, s.Cpad, c->m, c->stream,
+                       BOCF_KIDS(c));
+  else
+    launch_cross_kernel(c->Xs.as<double>(), c->xs_stride, c->N, c->Np, c->d, c->kernel_id, c->hypd.as<KernHyp>(), c->Xc.as<double>(), s.c0, s.Cn,
+                        s.Cpad, s.w, c->Kstar.as<double>(), s.Cpad, (long)c->Np * s.Cpad, mp, mp + p.mean_plane, nsplit_for(c->Np, s.Cpad, c->m), c->m,
+                        p.kind == PRED_MEAN ? 0 : (p.kind == PRED_F32 ? 2 : 1), c->stream, BOCF_KIDS(c));
+  if (!p.mean_with_var)
+    launch_finalize_mean(mp, mp + p.mean_plane, p.nrt, s.Cpad, c->hypd.as<KernHyp>(), c->mean.as<double>(), p.ld, s.c0, s.Cn, c->m, c->stream);
+}
+
+// variances of the pass from `rows` partial sums of squares per column, and its means from their partials, in one launch
+static void predict_finalize(bocf_ctx* c, const PredictPass& s, int rows) {
+  double* mp = c->meanpart.as<double>();
+  launch_finalize_var(c->sumsq.as<double>(), rows, s.Cpad, c->hypd.as<KernHyp>(), s.flags, c->var.as<double>(), s.p.ld, s.c0, s.Cn, c->m, c->stream, mp,
+                      mp + s.p.mean_plane, s.p.nrt, c->mean.as<double>());
+}
+
+// n <= 16: GEMV-shaped, R streamed once per product (single-point L-BFGS calls); gradients: W = R V from R^T, then dk/dx
+static void contract_small(bocf_ctx* c, const PredictPass& s) {
+  const int Np = c->Np, nc = small_width(s.Cn);
+  const long strideS = (long)Np * Np;
+  launch_gemv_small_t_mfma(c->R.as<double>(), strideS, Np, c->Kstar.as<double>(), s.Cpad, (long)Np * s.Cpad, c->Vs.as<double>(), c->sumsq.as<double>(),
+                           s.Cpad, nc, c->m, c->stream);
+  predict_finalize(c, s, Np / 16);
+  if (!s.need_grad) return;
+  launch_gemv_small_n_mfma(c->RT.as<double>(), strideS, Np, c->Vs.as<double>(), c->Ws.as<double>(), nc, c->m, c->stream);
+  launch_grad_kernel(c->Xs.as<double>(), c->xs_stride, c->N, Np, c->d, c->kernel_id, c->hypd.as<KernHyp>(), c->Xc.as<double>(), s.c0, s.Cn, s.w,
+                     c->Ws.as<double>(), nc, (long)Np * nc, c->dmean.as<double>(), c->dvar.as<double>(), s.p.ld, c->m, c->stream, BOCF_KIDS(c));
+}
+
+// gradients need w = Ky^-1 k* = R (R^T k*): V = R^T K* stored this time, then W = R V (R k-major = RT);
+// W overwrites the K* buffer (no longer needed: the gradient kernel recomputes dk/dx from the inputs)
+static void predict_gradients(bocf_ctx* c, const PredictPass& s) {
+  const int Np = c->Np;
+  GemmArgs v{};
+  v.A = c->R.as<double>(); v.lda = Np; v.strideA = (long)Np * Np;
+  v.B = c->Kstar.as<double>(); v.ldb = s.Cpad; v.strideB = (long)Np * s.Cpad;
+  v.Cin = nullptr; v.Cout = c->Vbuf.as<double>(); v.ldc = s.Cpad; v.strideC = (long)Np * s.Cpad;
+  v.M = Np; v.Ncols = s.Cpad; v.K = Np; v.kb = BOCF_TILE; v.krt = BOCF_TILE; v.rt_desc = 1; v.alpha = 1.0;
+  launch_gemm_f64(v, c->m, 0, c->stream);
+  GemmArgs w{};
+  w.A = c->RT.as<double>(); w.lda = Np; w.strideA = (long)Np * Np;
+  w.B = c->Vbuf.as<double>(); w.ldb = s.Cpad; w.strideB = (long)Np * s.Cpad;
+  w.Cin = nullptr; w.Cout = c->Kstar.as<double>(); w.ldc = s.Cpad; w.strideC = (long)Np * s.Cpad;
+  w.M = Np; w.Ncols = s.Cpad; w.K = Np; w.kb = Np; w.kbeg_rt = BOCF_TILE; w.alpha = 1.0;
+  launch_gemm_f64(w, c->m, 0, c->stream);
+  launch_grad_kernel(c->Xs.as<double>(), c->xs_stride, c->N, Np, c->d, c->kernel_id, c->hypd.as<KernHyp>(), c->Xc.as<double>(), s.c0, s.Cn, s.w,
+                     c->Kstar.as<double>(), s.Cpad, (long)Np * s.Cpad, c->dmean.as<double>(), c->dvar.as<double>(), s.p.ld, c->m, c->stream, BOCF_KIDS(c));
+}
+
+// V = R^T K*, only its column sums of squares leave the chip: the three-buffer kernel, whose loop keeps the vector ALU free and skips the zero
+// blocks of R's diagonal range (gemm_f64.hip), in the plan's tiling; then the gradients
+static void contract_f64(bocf_ctx* c, const PredictPass& s) {
+  const int Np = c->Np;
+  GemmArgs g{};
+  g.A = c->R.as<double>(); g.lda = Np; g.strideA = (long)Np * Np;
+  g.B = c->Kstar.as<double>(); g.ldb = s.Cpad; g.strideB = (long)Np * s.Cpad;
+  g.M = Np; g.Ncols = s.Cpad; g.K = Np; g.kb = BOCF_TILE; g.krt = BOCF_TILE; g.rt_desc = 1;
+  g.swizzle = s.p.tiling(s.Cpad);
+  g.vprobe = c->kstar_valu_probe;
+  g.prefetch1 = c->prefetch1;
+  g.sumsq = c->sumsq.as<double>(); g.strideSumsq = (long)s.p.nrt * s.Cpad;
+  {
+    KernelTimer t(c, s.Cn);
+    launch_gemm_f64(g, c->m, 1, c->stream);
+  }
+  predict_finalize(c, s, s.p.nrt);
+  if (s.need_grad) predict_gradients(c, s);
+}
+
+// fp32 variance contraction (BASELINE configs[4]): K* stored as fp32 by the cross kernel, R32 = (float) R
+static void contract_f32(bocf_ctx* c, const PredictPass& s) {
+  const int Np = c->Np;
+  GemmArgs32 g{};
+  g.A = c->R32.as<float>(); g.lda = Np; g.strideA = (long)Np * Np;
+  g.B = c->Kstar.as<float>(); g.ldb = s.Cpad; g.strideB = (long)Np * s.Cpad;
+  g.M = Np; g.Ncols = s.Cpad; g.K = Np;
+  g.sumsq = c->sumsq.as<double>(); g.strideSumsq = (long)s.p.nrt * s.Cpad;
+  g.tile128 = s.p.swizzle == 0;
+  {
+    KernelTimer t(c, s.Cn);
+    launch_gemm_f32_sumsq(g, c->m, c->stream);
+  }
+  predict_finalize(c, s, s.p.nrt);
+}
+
+// int8 (Ozaki): the pass's K* -> digit fragments, then the exact int8 contraction; same partial sums' layout, same finalisation
+static void contract_i8(bocf_ctx* c, const PredictPass& s) {
+  const int Np = c->Np;
+  {
+    KernelTimer t(c, s.Cn);
+    launch_slice_operand(c->Kstar.as<double>(), s.Cpad, (long)Np * s.Cpad, Np, Np, s.Cpad, c->Ki8e.as<int>(), 0, c->Ki8.p, c->m, c->stream);
+    launch_var_i8(c->Ri8.p, c->Ki8.p, Np, s.Cpad, c->Ri8e.as<int>(), c->Ki8e.as<int>(), c->sumsq.as<double>(), (long)s.p.nrt * s.Cpad, c->m, c->stream,
+                  c->i8_group);
+  }
+  predict_finalize(c, s, s.p.nrt);
+}
+
+// the int8 operands that last as long as the fit: R's digit fragments and column exponents, and ONE scale per output for every column of K*
+// (a stationary kernel never exceeds its variance)
+static int prepare_i8(bocf_ctx* c) {
+  const int Np = c->Np, m = c->m;
+  HIPCHK(hipMemsetAsync(c->Ri8e.p, 0x80, sizeof(int) * (size_t)m * Np, c->stream));      // (below any exponent: the kernel takes maxima)
+  launch_col_exponents(c->R.as<double>(), (long)Np * Np, Np, c->Ri8e.as<int>(), m, c->stream);
+  launch_slice_operand(c->R.as<double>(), Np, (long)Np * Np, Np, Np, Np, c->Ri8e.as<int>(), Np, c->Ri8.p, m, c->stream);
+  std::vector<int> eb(m);
+  for (int j = 0; j < m; ++j) eb[j] = c->hyp[j].variance > 0.0 ? ilogb(c->hyp[j].variance) + 1 : 0;
+  HIPCHK(hipMemcpyAsync(c->Ki8e.p, eb.data(), sizeof(int) * m, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));             // (eb goes out of scope)
+  c->ri8_valid = true;
+  return 0;
+}
+
+// mean / var of all resident candidates into c->mean / c->var (m, pred_cap); w: the mean weights (nullptr: alpha)
+static int run_predict(bocf_ctx* c, int flags, bool need_var, bool need_grad = false, const double* w = nullptr) {
+  const int C = c->C;
   if (C == 0) return 0;
   if (c->canned) {           // mean / var were given by the host (bocf_set_posterior): nothing to predict
     if (need_grad) return fail("predict", "a host-given posterior carries no gradients");
     return 0;
   }
-  const int nrt = Np / BOCF_TILE;
-  // candidates per pass: option "chunk", lowered so that the K* (and, for gradients, V) workspace of ALL fitted outputs
-  // (hyper-samples x outputs) stays inside option "workspace_mb"; results do not depend on the chunking
-  long chunk = c->chunk;
-  {
-    const double per_col = (double)m * Np * sizeof(double) * (need_grad ? 2.0 : 1.0);
-    long fit_cols = (long)((double)c->workspace_mb * 1048576.0 / per_col);
-    fit_cols = fit_cols / BOCF_TILE * BOCF_TILE;
-    if (fit_cols < BOCF_TILE) fit_cols = BOCF_TILE;
-    if (chunk > fit_cols) chunk = fit_cols;
-  }
-  const int chunkpad = (int)(C < chunk ? round_up(C, BOCF_TILE) : chunk);
-  if (c->pred_cap < C) {
-    const int cap = round_up(C, BOCF_TILE);
-    if (c->mean.ensure(sizeof(double) * (size_t)m * cap) || c->var.ensure(sizeof(double) * (size_t)m * cap) ||
-        c->acq.ensure(sizeof(double) * cap))
-      return -1;
-    c->pred_cap = cap;
-  }
-  // pred_cap may have been sized for another m: keep the leading dimension explicit
-  const long ld = c->pred_cap;
-  if (c->mean.ensure(sizeof(double) * (size_t)m * ld) || c->var.ensure(sizeof(double) * (size_t)m * ld)) return -1;
-  if (need_var) {
-    // (the small path keeps one partial per 16-row tile)
-    if (c->Kstar.ensure(sizeof(double) * (size_t)m * Np * chunkpad) || c->sumsq.ensure(sizeof(double) * (size_t)m * (C <= BOCF_SMALL_N ? Np / 16 : nrt) * chunkpad)) return -1;
-  }
-  const bool small = C <= BOCF_SMALL_N && c->small_path;
-  // fp32 variance contraction (BASELINE configs[4]): K* stored as fp32, R32 = (float) R; the fit, the mean
-  // (whose alpha-weighted sum cancels catastrophically in fp32) and the gradient path stay in fp64
-  const bool f32 = c->predict_f32 && need_var && !need_grad && !small;
-  if (f32 && !c->r32_valid) {
-    if (c->R32.ensure(sizeof(float) * (size_t)m * Np * Np)) return -1;
-    launch_f64_to_f32(c->R.as<double>(), c->R32.as<float>(), (long)m * Np * Np, c->stream);
+  PredictPlanInput in;
+  in.C = C; in.N = c->N; in.Np = c->Np; in.m = c->m; in.d = c->d; in.pred_cap = c->pred_cap;
+  in.need_var = need_var; in.need_grad = need_grad;
+  in.chunk = c->chunk; in.workspace_mb = c->workspace_mb;
+  in.small_path = c->small_path; in.predict_f32 = c->predict_f32; in.predict_i8 = c->predict_i8; in.swizzle = c->swizzle;
+  const PredictPlan p = plan_predict(in);
+  // grow the workspace (R's fp32 copy and int8 operands only where the fit has none yet), then the operands that last for the fit
+  DevBuf* bufs[] = {&c->mean, &c->var, &c->acq, &c->Kstar, &c->sumsq, &c->R32, &c->Ki8, &c->Ki8e, &c->Ri8, &c->Ri8e,
+                    &c->Vs, &c->Ws, &c->Vbuf, &c->dmean, &c->dvar, &c->dacq, &c->meanpart};
+  const size_t bytes[] = {p.mean_bytes, p.var_bytes, p.acq_bytes, p.kstar_bytes, p.sumsq_bytes, c->r32_valid ? 0 : p.r32_bytes, p.ki8_bytes, p.ki8e_bytes,
+                          c->ri8_valid ? 0 : p.ri8_bytes, c->ri8_valid ? 0 : p.ri8e_bytes, p.vs_bytes, p.ws_bytes, p.vbuf_bytes, p.dmean_bytes,
+                          p.dvar_bytes, p.dacq_bytes, p.meanpart_bytes};
+  for (size_t i = 0; i < sizeof(bytes) / sizeof(bytes[0]); ++i)
+    if (bufs[i]->ensure(bytes[i])) return -1;
+  c->pred_cap = p.ld;
+  if (p.kind == PRED_F32 && !c->r32_valid) {
+    launch_f64_to_f32(c->R.as<double>(), c->R32.as<float>(), (long)c->m * c->Np * c->Np, c->stream);
     c->r32_valid = true;
   }
-  // int8 (Ozaki) contraction: from 128 candidates up, variances only (the gradient path needs V itself)
-  const bool i8 = c->predict_i8 && need_var && !need_grad && !small && !f32 && Np <= 16384;   // (int32 group sums: 6 x 127^2 x N < 2^31)
-  if (i8) {
-    if (c->Ki8.ensure(i8_operand_bytes(Np, chunkpad, m)) || c->Ki8e.ensure(sizeof(int) * m)) return -1;
-    if (!c->ri8_valid) {
-      if (c->Ri8.ensure(i8_operand_bytes(Np, Np, m)) || c->Ri8e.ensure(sizeof(int) * (size_t)m * Np)) return -1;
-      HIPCHK(hipMemsetAsync(c->Ri8e.p, 0x80, sizeof(int) * (size_t)m * Np, c->stream));      // (below any exponent: the kernel takes maxima)
-      launch_col_exponents(c->R.as<double>(), (long)Np * Np, Np, c->Ri8e.as<int>(), m, c->stream);
-      launch_slice_operand(c->R.as<double>(), Np, (long)Np * Np, Np, Np, Np, c->Ri8e.as<int>(), Np, c->Ri8.p, m, c->stream);
-      // a stationary kernel never exceeds its variance: ONE scale for every column of K*
-      std::vector<int> eb(m);
-      for (int j = 0; j < m; ++j) eb[j] = c->hyp[j].variance > 0.0 ? ilogb(c->hyp[j].variance) + 1 : 0;
-      HIPCHK(hipMemcpyAsync(c->Ki8e.p, eb.data(), sizeof(int) * m, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));             // (eb goes out of scope)
-      c->ri8_valid = true;
+  if (p.kind == PRED_I8 && !c->ri8_valid && prepare_i8(c)) return -1;
+  // per pass: K* and the mean partials, the contraction, the finalisation
+  for (long c0 = 0; c0 < C; c0 += p.chunk) {
+    const int Cn = (int)((C - c0) < p.chunk ? (C - c0) : p.chunk);
+    const PredictPass s{p, w ? w : c->alpha.as<double>(), flags, need_grad, (int)c0, Cn, round_up(Cn, BOCF_TILE)};
+    predict_cross(c, s);
+    switch (p.kind) {
+      case PRED_MEAN: break;
+      case PRED_SMALL: contract_small(c, s); break;
+      case PRED_F64: contract_f64(c, s); break;
+      case PRED_F32: contract_f32(c, s); break;
+      case PRED_I8: contract_i8(c, s); break;
     }
-  }
-  if (small && need_var) {
-    if (c->Vs.ensure(sizeof(double) * (size_t)m * Np * BOCF_SMALL_N) || c->Ws.ensure(sizeof(double) * (size_t)m * Np * BOCF_SMALL_N)) return -1;
-  }
-  if (need_grad) {
-    if ((!small && c->Vbuf.ensure(sizeof(double) * (size_t)m * Np * chunkpad)) || c->dmean.ensure(sizeof(double) * (size_t)m * ld * d) ||
-        c->dvar.ensure(sizeof(double) * (size_t)m * ld * d) || c->dacq.ensure(sizeof(double) * (size_t)ld * d))
-      return -1;
-  }
-  const size_t mean_plane = (size_t)m * nrt * (chunkpad > Np ? chunkpad : Np);     // partial means per 128-row block: hi plane, lo plane
-  if (c->meanpart.ensure(sizeof(double) * 2 * mean_plane)) return -1;
-  const long strideS = (long)Np * Np;
-  for (long c0 = 0; c0 < C; c0 += chunk) {
-    const int Cn = (int)((C - c0) < chunk ? (C - c0) : chunk);
-    const int Cpad = round_up(Cn, BOCF_TILE);
-    // The chunk is processed in up to 4 column parts: part i's K* build (VALU + HBM writes, stream2)
-    // runs underneath part i-1's contraction (MFMA, main stream).  Parts share the chunk's buffers
-    // (disjoint column ranges), and per-candidate results do not depend on the partition.
-    int nparts = 1;
-    if (c->overlap && need_var && !(C <= BOCF_SMALL_N && c->small_path)) nparts = Cpad >= 32768 ? 4 : (Cpad >= 8192 ? 2 : 1);
-    if (nparts > 1) {
-      while ((int)c->ev_parts.size() < nparts) {
-        hipEvent_t ev;
-        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        c->ev_parts.push_back(ev);
-      }
-      HIPCHK(hipEventRecord(c->ev_start, c->stream));
-      HIPCHK(hipStreamWaitEvent(c->stream2, c->ev_start, 0));
-    }
-    const int part_cols = round_up((Cpad + nparts - 1) / nparts, BOCF_TILE);
-    for (int part = 0; part < nparts; ++part) {
-      const int pc0 = part * part_cols;                       // first column of the part inside the chunk
-      if (pc0 >= Cpad) break;
-      const int pcols = (pc0 + part_cols <= Cpad) ? part_cols : (Cpad - pc0);
-      const int pvalid = Cn - pc0 < 0 ? 0 : (Cn - pc0 < pcols ? Cn - pc0 : pcols);
-      hipStream_t sx = nparts > 1 ? c->stream2 : c->stream;
-      const int ns = nsplit_for(Np, pcols, m);
-      double* kbase = f32 ? reinterpret_cast<double*>(c->Kstar.as<float>() + pc0) : c->Kstar.as<double>() + pc0;
-      PhaseTimer t_cross(c, nparts > 1 ? "cross_overlapped" : "cross");
-      if (nparts > 1) t_cross.stop();        // (events belong to the main stream; the overlapped build runs on stream2)
-      // (<= 16 candidates with variances: the small path on the matrix pipe -- K* and the same mean partials from cross_small_kernel)
-      const bool small_mfma = small && need_var && !f32;
-      int nc_small = 1;
-      while (nc_small < Cn) nc_small *= 2;
-      if (small_mfma)
-        launch_cross_small(c->Xs.as<double>(), c->xs_stride, N, Np, d, c->kernel_id, c->hypd.as<KernHyp>(), c->Xc.as<double>(), (int)c0, Cn, nc_small,
-                           c->alpha.as<double>(), c->Kstar.as<double>(), Cpad, (long)Np * Cpad, c->meanpart.as<double>(),
-                           c->meanpart.as<double>() + mean_plane, pcols, m, sx, BOCF_KIDS(c));
-      else
-      launch_cross_kernel(c->Xs.as<double>(), c->xs_stride, N, Np, d, c->kernel_id, c->hypd.as<KernHyp>(), c->Xc.as<double>(),
-                          (int)c0 + pc0, pvalid, pcols, c->alpha.as<double>(), kbase, Cpad, (long)Np * Cpad,
-                          c->meanpart.as<double>() + (size_t)pc0 * m * nrt, c->meanpart.as<double>() + mean_plane + (size_t)pc0 * m * nrt, ns, m,
-                          need_var ? (f32 ? 2 : 1) : 0, sx, BOCF_KIDS(c));
-      // (a part that goes on to the big contraction on the same stream finishes its means in the launch that finishes its variances)
-      const bool mean_with_var = need_var && nparts == 1 && (!small || small_mfma);
-      if (!mean_with_var)
-        launch_finalize_mean(c->meanpart.as<double>() + (size_t)pc0 * m * nrt, c->meanpart.as<double>() + mean_plane + (size_t)pc0 * m * nrt, nrt,
-                             pcols, c->hypd.as<KernHyp>(), c->mean.as<double>(), ld, (int)c0 + pc0, pvalid, m, sx);
-      const double* mp_hi = mean_with_var ? c->meanpart.as<double>() + (size_t)pc0 * m * nrt : nullptr;
-      const double* mp_lo = mean_with_var ? c->meanpart.as<double>() + mean_plane + (size_t)pc0 * m * nrt : nullptr;
-      t_cross.stop();
-      if (!need_var) continue;
-      if (nparts > 1) {
-        HIPCHK(hipEventRecord(c->ev_parts[part], c->stream2));
-        HIPCHK(hipStreamWaitEvent(c->stream, c->ev_parts[part], 0));
-      }
-      if (small) {
-        // n <= 16: GEMV-shaped, R streamed once per product (single-point L-BFGS calls)
-        const int nc = nc_small;
-        if (small_mfma) {
-          launch_gemv_small_t_mfma(c->R.as<double>(), strideS, Np, c->Kstar.as<double>(), Cpad, (long)Np * Cpad, c->Vs.as<double>(), c->sumsq.as<double>(), Cpad,
-                                   nc, m, c->stream);
-          launch_finalize_var(c->sumsq.as<double>(), Np / 16, Cpad, c->hypd.as<KernHyp>(), flags, c->var.as<double>(), ld, (int)c0, Cn, m, c->stream, mp_hi,
-                              mp_lo, nrt, c->mean.as<double>());
-        } else {
-          launch_gemv_small_t(c->R.as<double>(), strideS, Np, c->Kstar.as<double>(), Cpad, (long)Np * Cpad, c->Vs.as<double>(), nc, m, c->stream);
-          launch_sumsq_small(c->Vs.as<double>(), Np, c->sumsq.as<double>(), Cpad, nc, m, c->stream);
-          launch_finalize_var(c->sumsq.as<double>(), 1, Cpad, c->hypd.as<KernHyp>(), flags, c->var.as<double>(), ld, (int)c0, Cn, m, c->stream);
-        }
-        if (need_grad) {
-          if (small_mfma) launch_gemv_small_n_mfma(c->RT.as<double>(), strideS, Np, c->Vs.as<double>(), c->Ws.as<double>(), nc, m, c->stream);
-          else launch_gemv_small_n(c->R.as<double>(), strideS, Np, c->Vs.as<double>(), c->Ws.as<double>(), nc, m, c->stream);
-          launch_grad_kernel(c->Xs.as<double>(), c->xs_stride, N, Np, d, c->kernel_id, c->hypd.as<KernHyp>(), c->Xc.as<double>(), (int)c0, Cn,
-                             c->alpha.as<double>(), c->Ws.as<double>(), nc, (long)Np * nc, c->dmean.as<double>(),
-                             c->dvar.as<double>(), ld, m, c->stream, BOCF_KIDS(c));
-        }
-        continue;
-      }
-      if (f32) {
-        GemmArgs32 g32{};
-        g32.A = c->R32.as<float>(); g32.lda = Np; g32.strideA = strideS;
-        g32.B = c->Kstar.as<float>() + pc0; g32.ldb = Cpad; g32.strideB = (long)Np * Cpad;
-        g32.M = Np; g32.Ncols = pcols; g32.K = Np;
-        g32.sumsq = c->sumsq.as<double>() + (size_t)pc0 * m * nrt; g32.strideSumsq = (long)nrt * pcols;
-        g32.tile128 = c->swizzle == 0;
-        hipEvent_t f0 = nullptr, f1 = nullptr;
-        if (c->profile) {
-          HIPCHK(hipEventCreate(&f0));
-          HIPCHK(hipEventCreate(&f1));
-          HIPCHK(hipEventRecord(f0, c->stream));
-        }
-        launch_gemm_f32_sumsq(g32, m, c->stream);
-        if (c->profile) {
-          HIPCHK(hipEventRecord(f1, c->stream));
-          c->events.emplace_back(f0, f1);
-          c->prof_flops += (double)m * (double)N * (double)N * (double)pvalid;
-        }
-        launch_finalize_var(c->sumsq.as<double>() + (size_t)pc0 * m * nrt, nrt, pcols, c->hypd.as<KernHyp>(), flags, c->var.as<double>(), ld,
-                            (int)c0 + pc0, pvalid, m, c->stream, mp_hi, mp_lo, nrt, c->mean.as<double>());
-        continue;
-      }
-      if (i8) {
-        // the part's K* -> digit fragments, then the exact int8 contraction; same partial sums' layout, same finalisation
-        hipEvent_t f0 = nullptr, f1 = nullptr;
-        if (c->profile) {
-          HIPCHK(hipEventCreate(&f0));
-          HIPCHK(hipEventCreate(&f1));
-          HIPCHK(hipEventRecord(f0, c->stream));
-        }
-        launch_slice_operand(c->Kstar.as<double>() + pc0, Cpad, (long)Np * Cpad, Np, Np, pcols, c->Ki8e.as<int>(), 0, c->Ki8.p, m, c->stream);
-        launch_var_i8(c->Ri8.p, c->Ki8.p, Np, pcols, c->Ri8e.as<int>(), c->Ki8e.as<int>(), c->sumsq.as<double>() + (size_t)pc0 * m * nrt, (long)nrt * pcols, m,
-                      c->stream, c->i8_group);
-        if (c->profile) {
-          HIPCHK(hipEventRecord(f1, c->stream));
-          c->events.emplace_back(f0, f1);
-          c->prof_flops += (double)m * (double)N * (double)N * (double)pvalid;
-        }
-        launch_finalize_var(c->sumsq.as<double>() + (size_t)pc0 * m * nrt, nrt, pcols, c->hypd.as<KernHyp>(), flags, c->var.as<double>(), ld,
-                            (int)c0 + pc0, pvalid, m, c->stream, mp_hi, mp_lo, nrt, c->mean.as<double>());
-        continue;
-      }
-      // V = R^T K*, only its column sums of squares leave the chip
-      GemmArgs g{};
-      g.A = c->R.as<double>(); g.lda = Np; g.strideA = strideS;
-      g.B = c->Kstar.as<double>() + pc0; g.ldb = Cpad; g.strideB = (long)Np * Cpad;
-      g.M = Np; g.Ncols = pcols; g.K = Np; g.kb = BOCF_TILE; g.krt = BOCF_TILE; g.rt_desc = 1;
-      // 256-row tiles (two 128-row tiles per workgroup share every K* fetch: 77.6 instead of 144 GB per launch at config 3,
-      // bit-identical sums) in the three-buffer kernel whose loop keeps the vector ALU free and skips the zero blocks of R's
-      // diagonal range (gemm_f64.hip): 0.93 of the fp64 MFMA peak against 0.83 for the 128-row kernel at N = 4096, 0.81 against
-      // 0.77 at config 2 (N = 1024, 8192 candidates); from 2048 candidates per pass up (below that its fewer, larger
-      // workgroups leave CUs idle: N = 1024, C = 1024: 0.49 against 0.40 ms for the 128-row kernel).  Padded sizes that are not
-      // a multiple of 256 fall back in the launcher.  Option "swizzle" = 0 / 256 / 257 / 258 forces a tiling.
-      g.swizzle = c->swizzle < 0 ? (pcols >= 2048 ? 258 : 0) : c->swizzle;
-      g.vprobe = c->kstar_valu_probe;
-      g.prefetch1 = c->prefetch1 || nparts > 1;     // 194 VGPRs: leaves room for the K*-build waves on the same SIMD
-      g.sumsq = c->sumsq.as<double>() + (size_t)pc0 * m * nrt; g.strideSumsq = (long)nrt * pcols;
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (c->profile) {
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
-        HIPCHK(hipEventRecord(e0, c->stream));
-      }
-      launch_gemm_f64(g, m, 1, c->stream);
-      if (c->profile) {
-        HIPCHK(hipEventRecord(e1, c->stream));
-        c->events.emplace_back(e0, e1);
-        c->prof_flops += (double)m * (double)N * (double)N * (double)pvalid;
-      }
-      launch_finalize_var(c->sumsq.as<double>() + (size_t)pc0 * m * nrt, nrt, pcols, c->hypd.as<KernHyp>(), flags, c->var.as<double>(), ld,
-                          (int)c0 + pc0, pvalid, m, c->stream, mp_hi, mp_lo, nrt, c->mean.as<double>());
-    }
-    if (small || !need_var) continue;
-    if (!need_grad) continue;
-    // gradients need w = Ky^-1 k* = R (R^T k*): V = R^T K* stored this time, then W = R V (R k-major = RT);
-    // W overwrites the K* buffer (no longer needed: the gradient kernel recomputes dk/dx from the inputs)
-    GemmArgs v{};
-    v.A = c->R.as<double>(); v.lda = Np; v.strideA = strideS;
-    v.B = c->Kstar.as<double>(); v.ldb = Cpad; v.strideB = (long)Np * Cpad;
-    v.Cin = nullptr; v.Cout = c->Vbuf.as<double>(); v.ldc = Cpad; v.strideC = (long)Np * Cpad;
-    v.M = Np; v.Ncols = Cpad; v.K = Np; v.kb = BOCF_TILE; v.krt = BOCF_TILE; v.rt_desc = 1; v.alpha = 1.0;
-    launch_gemm_f64(v, m, 0, c->stream);
-    GemmArgs w{};
-    w.A = c->RT.as<double>(); w.lda = Np; w.strideA = strideS;
-    w.B = c->Vbuf.as<double>(); w.ldb = Cpad; w.strideB = (long)Np * Cpad;
-    w.Cin = nullptr; w.Cout = c->Kstar.as<double>(); w.ldc = Cpad; w.strideC = (long)Np * Cpad;
-    w.M = Np; w.Ncols = Cpad; w.K = Np; w.kb = Np; w.kbeg_rt = BOCF_TILE; w.alpha = 1.0;
-    launch_gemm_f64(w, m, 0, c->stream);
-    launch_grad_kernel(c->Xs.as<double>(), c->xs_stride, N, Np, d, c->kernel_id, c->hypd.as<KernHyp>(), c->Xc.as<double>(), (int)c0, Cn,
-                       c->alpha.as<double>(), c->Kstar.as<double>(), Cpad, (long)Np * Cpad, c->dmean.as<double>(), c->dvar.as<double>(), ld,
-                       m, c->stream, BOCF_KIDS(c));
   }
   LAUNCHCHK();
   return 0;
@@ -605,13 +530,7 @@ extern "C" int bocf_predict_cov_column(bocf_ctx* c, int flags, double* cov_out) 
                       c->meanpart.as<double>() + plane, 1, m, 1, c->stream, BOCF_KIDS(c));
   launch_gemv_small_t(c->R.as<double>(), strideS, Np, c->Kstar.as<double>(), BOCF_TILE, (long)Np * BOCF_TILE, c->tvec.as<double>(), 1, m, c->stream);
   launch_gemv_upper_n(c->R.as<double>(), strideS, Np, c->tvec.as<double>(), c->dvec.as<double>(), m, c->stream);
-  // the mean pass reads c->alpha: lend it w for one pass (c->mean then holds K(x_i, X) w + ymean)
-  std::swap(c->alpha.p, c->dvec.p);
-  std::swap(c->alpha.cap, c->dvec.cap);
-  const int rc = run_predict(c, 0, false);
-  std::swap(c->alpha.p, c->dvec.p);
-  std::swap(c->alpha.cap, c->dvec.cap);
-  if (rc) return -1;
+  if (run_predict(c, 0, false, false, c->dvec.as<double>())) return -1;   // (c->mean then holds K(x_i, X) w + ymean)
   if (c->var.ensure(sizeof(double) * (size_t)m * c->pred_cap)) return -1;
   launch_cov_column(c->Xc.as<double>(), c->C, d, c->kernel_id, c->hypd.as<KernHyp>(), c->mean.as<double>(), c->pred_cap, flags, c->var.as<double>(),
                     c->pred_cap, m, c->stream, BOCF_KIDS(c));
@@ -701,17 +620,11 @@ static int copy_pair_out(bocf_ctx* c, const void* src0, double* out0, size_t b0,
   return 0;
 }
 
-// acquisition values (and gradients) to the host
-static int finish_acq(bocf_ctx* c, double* acq_out, double* dacq_out = nullptr) {
-  c->have_acq = true;
-  const size_t b0 = acq_out ? sizeof(double) * (size_t)c->C : 0, b1 = dacq_out ? sizeof(double) * (size_t)c->C * c->d : 0;
-  return copy_pair_out(c, c->acq.p, acq_out, b0, c->dacq.p, dacq_out, b1);
-}
+typedef void (*AcqLaunch)(const AcqArgs& a, hipStream_t s);
 
 // The reference's h-loop (maEI.py:85-97, uEI_noiseless.py:71-82) runs here: hyper-sample h reads rows
 // [h*m, (h+1)*m) of the mean / variance / gradient buffers and adds its share (1/H) to acq (and dacq).
-template <typename Launch>
-static int acq_over_hyper_samples(bocf_ctx* c, AcqArgs a, int m, int linear, Launch launch) {
+static void acq_over_hyper_samples(bocf_ctx* c, AcqArgs a, int m, int linear, AcqLaunch launch) {
   const int H = (c->acq_hyper_samples > 0 && c->acq_hyper_samples < c->hyper_samples) ? c->acq_hyper_samples : c->hyper_samples;
   const double* mean = a.mean; const double* var = a.var; const double* dmean = a.dmean; const double* dvar = a.dvar;
   for (int h = 0; h < H; ++h) {
@@ -735,7 +648,29 @@ static int acq_over_hyper_samples(bocf_ctx* c, AcqArgs a, int m, int linear, Lau
     PhaseTimer t(c, "acq");
     launch(a, c->stream);
   }
-  return 0;
+}
+
+// What the four acquisitions share once their arguments are checked: the parameters go up (only when they changed), the posterior -- with
+// its input gradients for the _grad forms -- of every resident candidate, one launch per hyper-sample, values (and gradients) to the host.
+// linear: the linear-utility forms (EI / PI of theta^T f); theta_dim as the caller gave it; the Monte-Carlo forms read the resident samples.
+static int run_acq(bocf_ctx* c, int m, bool linear, bool grad, AcqLaunch launch, int kind, int util_kind, const double* util_params, int n_util_params,
+                   const double* theta, int theta_dim, const double* prob, int L, double* acq_out, double* dacq_out) {
+  HIPCHK(hipSetDevice(c->device));
+  if (c->C == 0) return 0;
+  if (upload_acq_params(c, theta, theta_dim, prob, L, util_params, n_util_params)) return -1;
+  // model.predict (maEI.py:87) / posterior_mean + posterior_variance (uEI_noiseless.py:73-74)
+  if (run_predict(c, BOCF_ADD_NOISE | BOCF_CLIP, true, grad)) return -1;
+  AcqArgs a{};
+  a.mean = c->mean.as<double>(); a.var = c->var.as<double>(); a.ld = c->pred_cap;
+  a.m = m; a.C = c->C; a.L = L; a.kind = kind; a.util_kind = util_kind; a.theta_dim = theta_dim > 0 ? theta_dim : 1;
+  a.theta = c->theta.as<double>(); a.prob = c->prob.as<double>(); a.best = c->best.as<double>();
+  a.util_params = c->params.as<double>(); a.n_util_params = n_util_params; a.acq = c->acq.as<double>();
+  if (!linear) { a.Wt = c->Wt.as<double>(); a.S = c->S_mc; }
+  if (grad) { a.dmean = c->dmean.as<double>(); a.dvar = c->dvar.as<double>(); a.ldg = c->pred_cap; a.d = c->d; a.dacq = c->dacq.as<double>(); }
+  acq_over_hyper_samples(c, a, m, linear ? 1 : 0, launch);
+  c->have_acq = true;
+  const size_t b0 = acq_out ? sizeof(double) * (size_t)c->C : 0, b1 = dacq_out ? sizeof(double) * (size_t)c->C * c->d : 0;
+  return copy_pair_out(c, c->acq.p, acq_out, b0, c->dacq.p, dacq_out, b1);
 }
 
 extern "C" int bocf_acq_linear(bocf_ctx* c, int kind, const double* theta, const double* prob, int L, double* acq_out) {
@@ -743,20 +678,8 @@ extern "C" int bocf_acq_linear(bocf_ctx* c, int kind, const double* theta, const
   if (kind != BOCF_ACQ_EI && kind != BOCF_ACQ_PI) return fail("bocf_acq_linear", "unknown acquisition kind");
   const int m = group_size(c, "bocf_acq_linear");
   if (m < 0) return -1;
-  HIPCHK(hipSetDevice(c->device));
-  if (c->C == 0) return 0;
-  if (upload_acq_params(c, theta, m, prob, L, nullptr, 0)) return -1;
-  if (run_predict(c, BOCF_ADD_NOISE | BOCF_CLIP, true)) return -1;        // model.predict (maEI.py:87)
-  AcqArgs a{};
-  a.mean = c->mean.as<double>(); a.var = c->var.as<double>(); a.ld = c->pred_cap;
-  a.m = m; a.C = c->C; a.L = L; a.kind = kind; a.util_kind = BOCF_UTIL_LINEAR; a.theta_dim = m;
-  a.theta = c->theta.as<double>(); a.prob = c->prob.as<double>(); a.best = c->best.as<double>();
-  a.util_params = c->params.as<double>(); a.acq = c->acq.as<double>();
-  if (acq_over_hyper_samples(c, a, m, 1, launch_acq_linear)) return -1;
-  return finish_acq(c, acq_out);
+  return run_acq(c, m, true, false, launch_acq_linear, kind, BOCF_UTIL_LINEAR, nullptr, 0, theta, m, prob, L, acq_out, nullptr);
 }
-
-static int finish_acq_grad(bocf_ctx* c, double* acq_out, double* dacq_out) { return finish_acq(c, acq_out, dacq_out); }
 
 extern "C" int bocf_acq_linear_grad(bocf_ctx* c, int kind, const double* theta, const double* prob, int L, double* acq_out,
                                     double* dacq_out) {
@@ -764,18 +687,7 @@ extern "C" int bocf_acq_linear_grad(bocf_ctx* c, int kind, const double* theta, 
   if (kind != BOCF_ACQ_EI && kind != BOCF_ACQ_PI) return fail("bocf_acq_linear_grad", "unknown acquisition kind");
   const int m = group_size(c, "bocf_acq_linear_grad");
   if (m < 0) return -1;
-  HIPCHK(hipSetDevice(c->device));
-  if (c->C == 0) return 0;
-  if (upload_acq_params(c, theta, m, prob, L, nullptr, 0)) return -1;
-  if (run_predict(c, BOCF_ADD_NOISE | BOCF_CLIP, true, true)) return -1;
-  AcqArgs a{};
-  a.mean = c->mean.as<double>(); a.var = c->var.as<double>(); a.ld = c->pred_cap;
-  a.m = m; a.C = c->C; a.L = L; a.kind = kind; a.util_kind = BOCF_UTIL_LINEAR; a.theta_dim = m;
-  a.theta = c->theta.as<double>(); a.prob = c->prob.as<double>(); a.best = c->best.as<double>();
-  a.util_params = c->params.as<double>(); a.acq = c->acq.as<double>();
-  a.dmean = c->dmean.as<double>(); a.dvar = c->dvar.as<double>(); a.ldg = c->pred_cap; a.d = c->d; a.dacq = c->dacq.as<double>();
-  if (acq_over_hyper_samples(c, a, m, 1, launch_acq_linear_grad)) return -1;
-  return finish_acq_grad(c, acq_out, dacq_out);
+  return run_acq(c, m, true, true, launch_acq_linear_grad, kind, BOCF_UTIL_LINEAR, nullptr, 0, theta, m, prob, L, acq_out, dacq_out);
 }
 
 extern "C" int bocf_set_mc_samples(bocf_ctx* c, const double* W, int S) {
@@ -793,57 +705,35 @@ extern "C" int bocf_set_mc_samples(bocf_ctx* c, const double* W, int S) {
   return 0;
 }
 
+// the utility checks of bocf_acq_mc and bocf_acq_mc_grad, in their order (errors name `me`): outputs per hyper-sample, or -1
+static int mc_group_size(bocf_ctx* c, const char* me, int util_kind, const double* util_params, int n_util_params, int theta_dim) {
+  if (util_kind < 0 || util_kind > BOCF_UTIL_ROSENBROCK) return fail(me, "unknown utility kind");
+  if (c->S_mc < 1) return fail(me, "no Monte-Carlo samples set (bocf_set_mc_samples)");
+  const int m = group_size(c, me);
+  if (m < 0) return -1;
+  if ((util_kind == BOCF_UTIL_LINEAR || util_kind == BOCF_UTIL_NEG_SQ_DIST) && theta_dim != m) return fail(me, "theta_dim must equal m");
+  if (util_kind == BOCF_UTIL_ROSENBROCK && (theta_dim < 1 || (m & 1))) return fail(me, "rosenbrock utility needs theta_dim >= 1 and even m");
+  if (util_kind == BOCF_UTIL_NEG_EXP_COS && n_util_params != m) return fail(me, "neg_exp_cos needs m weights");
+  if (n_util_params > 0 && !util_params) return fail(me, "util_params is null");
+  return m;
+}
+
 extern "C" int bocf_acq_mc(bocf_ctx* c, int kind, int util_kind, const double* util_params, int n_util_params, const double* theta,
                            int theta_dim, const double* prob, int L, double* acq_out) {
   if (!c || !c->fitted) return fail("bocf_acq_mc", "model not fitted");
   if (kind != BOCF_ACQ_EI && kind != BOCF_ACQ_PI) return fail("bocf_acq_mc", "unknown acquisition kind");
-  if (util_kind < 0 || util_kind > BOCF_UTIL_ROSENBROCK) return fail("bocf_acq_mc", "unknown utility kind");
-  if (c->S_mc < 1) return fail("bocf_acq_mc", "no Monte-Carlo samples set (bocf_set_mc_samples)");
-  const int m = group_size(c, "bocf_acq_mc");
+  const int m = mc_group_size(c, "bocf_acq_mc", util_kind, util_params, n_util_params, theta_dim);
   if (m < 0) return -1;
-  if ((util_kind == BOCF_UTIL_LINEAR || util_kind == BOCF_UTIL_NEG_SQ_DIST) && theta_dim != m) return fail("bocf_acq_mc", "theta_dim must equal m");
-  if (util_kind == BOCF_UTIL_ROSENBROCK && (theta_dim < 1 || (m & 1))) return fail("bocf_acq_mc", "rosenbrock utility needs theta_dim >= 1 and even m");
-  if (util_kind == BOCF_UTIL_NEG_EXP_COS && n_util_params != m) return fail("bocf_acq_mc", "neg_exp_cos needs m weights");
-  if (n_util_params > 0 && !util_params) return fail("bocf_acq_mc", "util_params is null");
-  HIPCHK(hipSetDevice(c->device));
-  if (c->C == 0) return 0;
-  if (upload_acq_params(c, theta, theta_dim, prob, L, util_params, n_util_params)) return -1;
-  if (run_predict(c, BOCF_ADD_NOISE | BOCF_CLIP, true)) return -1;        // posterior_mean + posterior_variance (uEI_noiseless.py:73-74)
-  AcqArgs a{};
-  a.mean = c->mean.as<double>(); a.var = c->var.as<double>(); a.ld = c->pred_cap;
-  a.m = m; a.C = c->C; a.L = L; a.kind = kind; a.util_kind = util_kind; a.theta_dim = theta_dim > 0 ? theta_dim : 1;
-  a.theta = c->theta.as<double>(); a.prob = c->prob.as<double>(); a.best = c->best.as<double>();
-  a.util_params = c->params.as<double>(); a.n_util_params = n_util_params;
-  a.Wt = c->Wt.as<double>(); a.S = c->S_mc; a.acq = c->acq.as<double>();
-  if (acq_over_hyper_samples(c, a, m, 0, launch_acq_mc)) return -1;
-  return finish_acq(c, acq_out);
+  return run_acq(c, m, false, false, launch_acq_mc, kind, util_kind, util_params, n_util_params, theta, theta_dim, prob, L, acq_out, nullptr);
 }
 
 extern "C" int bocf_acq_mc_grad(bocf_ctx* c, int util_kind, const double* util_params, int n_util_params, const double* theta,
                                 int theta_dim, const double* prob, int L, double* acq_out, double* dacq_out) {
   if (!c || !c->fitted) return fail("bocf_acq_mc_grad", "model not fitted");
-  if (util_kind < 0 || util_kind > BOCF_UTIL_ROSENBROCK) return fail("bocf_acq_mc_grad", "unknown utility kind");
-  if (c->S_mc < 1) return fail("bocf_acq_mc_grad", "no Monte-Carlo samples set (bocf_set_mc_samples)");
-  const int m = group_size(c, "bocf_acq_mc_grad");
+  const int m = mc_group_size(c, "bocf_acq_mc_grad", util_kind, util_params, n_util_params, theta_dim);
   if (m < 0) return -1;
-  if ((util_kind == BOCF_UTIL_LINEAR || util_kind == BOCF_UTIL_NEG_SQ_DIST) && theta_dim != m) return fail("bocf_acq_mc_grad", "theta_dim must equal m");
-  if (util_kind == BOCF_UTIL_ROSENBROCK && (theta_dim < 1 || (m & 1))) return fail("bocf_acq_mc_grad", "rosenbrock utility needs theta_dim >= 1 and even m");
-  if (util_kind == BOCF_UTIL_NEG_EXP_COS && n_util_params != m) return fail("bocf_acq_mc_grad", "neg_exp_cos needs m weights");
-  if (n_util_params > 0 && !util_params) return fail("bocf_acq_mc_grad", "util_params is null");
   if (c->d > 64) return fail("bocf_acq_mc_grad", "input dimension too large");
-  HIPCHK(hipSetDevice(c->device));
-  if (c->C == 0) return 0;
-  if (upload_acq_params(c, theta, theta_dim, prob, L, util_params, n_util_params)) return -1;
-  if (run_predict(c, BOCF_ADD_NOISE | BOCF_CLIP, true, true)) return -1;
-  AcqArgs a{};
-  a.mean = c->mean.as<double>(); a.var = c->var.as<double>(); a.ld = c->pred_cap;
-  a.m = m; a.C = c->C; a.L = L; a.kind = BOCF_ACQ_EI; a.util_kind = util_kind; a.theta_dim = theta_dim > 0 ? theta_dim : 1;
-  a.theta = c->theta.as<double>(); a.prob = c->prob.as<double>(); a.best = c->best.as<double>();
-  a.util_params = c->params.as<double>(); a.n_util_params = n_util_params;
-  a.Wt = c->Wt.as<double>(); a.S = c->S_mc; a.acq = c->acq.as<double>();
-  a.dmean = c->dmean.as<double>(); a.dvar = c->dvar.as<double>(); a.ldg = c->pred_cap; a.d = c->d; a.dacq = c->dacq.as<double>();
-  if (acq_over_hyper_samples(c, a, m, 0, launch_acq_mc_grad)) return -1;
-  return finish_acq_grad(c, acq_out, dacq_out);
+  return run_acq(c, m, false, true, launch_acq_mc_grad, BOCF_ACQ_EI, util_kind, util_params, n_util_params, theta, theta_dim, prob, L, acq_out, dacq_out);
 }
 
 extern "C" int bocf_set_eu_samples(bocf_ctx* c, const double* Z, int L, int S) {

@@ -299,8 +299,6 @@ __global__ __launch_bounds__(512, 1) void var_i8_kernel(const v4i_t* __restrict_
   if (ntot > nchL) finish(rtH);
 }
 
-size_t i8_operand_bytes(int Np, int ncols, int m) { return (size_t)m * BOCF_I8_SLICES * (size_t)(Np / 64) * (size_t)(ncols / 16) * 1024; }
-
 // (expo must hold the byte pattern 0x80 on entry: the caller's memset)
 void launch_col_exponents(const double* R, long strideR, int Np, int* expo, int m, hipStream_t s) {
   const unsigned nb = (unsigned)((Np + 255) / 256);

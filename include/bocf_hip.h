@@ -58,7 +58,7 @@ void bocf_destroy(bocf_ctx* ctx);
  * Sizes / plumbing:
  *   "chunk" = max candidates per pass (multiple of 128; default 65536), "workspace_mb" = cap of the per-pass K* workspace (default
  *   24576; the chunk is lowered to fit), "profile" = 1 records HIP events around the dominant (variance-GEMM) kernel and the named phases,
- *   "small_path" = 0 disables the GEMV-shaped path for <= 16 candidates, "overlap" = 1 builds K* on a second stream, "prefetch1".
+ *   "small_path" = 0 disables the GEMV-shaped path for <= 16 candidates, "prefetch1".
  * Semantics (kind 1):
  *   "predict_f32" = 1 runs the O(N^2 C) variance contraction in fp32 (K* and the inverse factor rounded to fp32, fp32 MFMA; fit, mean and
  *     gradients stay fp64) -- the arithmetic BASELINE configs[4] names,

@@ -233,7 +233,7 @@ def test_ragged_and_chunked(B):
     np.testing.assert_array_equal(mean1[:, 0], mean_full[:, 5])
     e_mean, e_var = model.predict(np.empty((0, d)))
     assert e_mean.shape == (m, 0) and e_var.shape == (m, 0)
-    for opt, val in (("swizzle", 258), ("overlap", 1), ("prefetch1", 1)):   # tiling / stream / staging options never change a number
+    for opt, val in (("swizzle", 258), ("prefetch1", 1)):   # tiling / staging options never change a number
         model.set_option(opt, val)
         mean_o, var_o = model.predict(p["Xc"])
         np.testing.assert_array_equal(mean_o, mean_full)
