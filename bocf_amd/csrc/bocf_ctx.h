@@ -90,6 +90,7 @@ struct bocf_ctx {
   int kinv_done = 0;         // the factorization schedule left Ky^-1 in the T scratch (an inference asked for it, bocf_plan_cholesky)
   int inverse_done = 0;      // the factorization schedule already produced R and R^T (team schedule)
   int ncu = 0;               // compute units of the device (read once, by bocf_create)
+  int* tile_ctr = nullptr;   // tile-queue counters of the variance contraction (two ints, zeroed by bocf_create; every launch leaves them zeroed)
   unsigned long long* team_tl = nullptr;   // probes build: task timeline of the team kernel (tools/team_timeline.py)
   int res_cus = 0;           // CUs currently reserved by s_res (0 = streams not created)
   int cu_masks_ok = 1;       // cleared when hipExtStreamCreateWithCUMask is refused: the single-stream schedules are used

@@ -107,6 +107,8 @@ struct GemmArgs {
   double alpha, beta;
   double* sumsq;               // epilogue 1: partial column sums of squares [batch][rt][Ncols]
   long strideSumsq;            // batch stride of sumsq
+  int* tile_ctr;               // 256-row variance kernel: two zeroed device counters (next tile, workgroups done) -> one workgroup per compute unit
+  int ncu;                     //   works through the tiles as a queue and leaves the counters zeroed; nullptr = one workgroup per tile
 };
 // epilogue 0: store C;  epilogue 1: write sumsq partials only (C is never stored)
 void launch_gemm_f64(const GemmArgs& g, int batch, int epilogue, hipStream_t s);

@@ -56,6 +56,14 @@ extern "C" int bocf_create(int device, bocf_ctx** out) {
     return fail("hipGetDeviceProperties", hipGetErrorString(e));
   }
   c->ncu = prop.multiProcessorCount;
+  e = hipMalloc((void**)&c->tile_ctr, 2 * sizeof(int));
+  if (e == hipSuccess) e = hipMemset(c->tile_ctr, 0, 2 * sizeof(int));
+  if (e != hipSuccess) {
+    if (c->tile_ctr) (void)hipFree(c->tile_ctr);
+    (void)hipStreamDestroy(c->stream);
+    delete c;
+    return fail("bocf_create: tile counters", hipGetErrorString(e));
+  }
   *out = c;
   return 0;
 }
@@ -103,6 +111,7 @@ extern "C" void bocf_destroy(bocf_ctx* c) {
                     &c->ts_X, &c->ts_K, &c->ts_V, &c->ts_mp, &c->ts_mu, &c->ts_Z, &c->ts_jit, &c->ts_u, &c->ts_theta, &c->ts_params, &c->ts_out};
   for (DevBuf* b : bufs) b->release();
   if (c->infer_out) (void)hipHostFree(c->infer_out);
+  if (c->tile_ctr) (void)hipFree(c->tile_ctr);
   for (hipEvent_t ev : c->ev_chol) (void)hipEventDestroy(ev);
   for (hipStream_t st : {c->s_res, c->s_hi, c->s_bulk, c->s_inv})
     if (st) (void)hipStreamDestroy(st);
@@ -376,6 +385,7 @@ static void contract_f64(bocf_ctx* c, const PredictPass& s) {
   g.vprobe = c->kstar_valu_probe;
   g.prefetch1 = c->prefetch1;
   g.sumsq = c->sumsq.as<double>(); g.strideSumsq = (long)s.p.nrt * s.Cpad;
+  g.tile_ctr = c->tile_ctr; g.ncu = c->ncu;
   {
     KernelTimer t(c, s.Cn);
     launch_gemm_f64(g, c->m, 1, c->stream);

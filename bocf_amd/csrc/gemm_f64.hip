@@ -484,15 +484,36 @@ struct IC {
 #define LDT3 128
 // STORE = 1: the same contraction with the 256 x 128 tile itself written out (alpha * acc, no read of C): the second product of an
 // inverse merge, RT21 = -R22^T-form x T'^T, has exactly the variance's shape (A upper triangular, row tile rt ends at 128 (rt + 1)).
-template <int STORE>
+// QUEUE = 1 (sum-of-squares form only): the grid is one workgroup per compute unit and every workgroup works through tiles -- its first is
+// blockIdx.x, each further one is claimed with ONE atomic add on g.tile_ctr[0] (issued when the diagonal range starts, handed to the
+// other waves through LDS when the epilogue starts), in the order the plain launch dispatches them (output slowest, heaviest row tile
+// first, column tile fastest); the claimed tile's first two operand tiles are requested during the epilogue.  A tile is computed exactly
+// as by the plain launch (same k order, same epilogue order: the same bits).  A workgroup never waits for another one: the counter is a
+// work queue, nothing else, so a busy or shared device makes the launch slower and cannot stall it.  The workgroup that leaves last --
+// every other one has then made its final, failing claim -- puts both counters back to zero for the next launch.
+template <int STORE, int QUEUE = 0>
 __global__ __launch_bounds__(512, 1) void gemm_tn_f64_sumsq256x3_kernel(GemmArgs g) {
+  static_assert(!(STORE && QUEUE), "the tile queue exists for the sum-of-squares epilogue only");
   __shared__ __attribute__((aligned(16))) double ldsA[3 * BK * LDA3];    //  98,304 B
   __shared__ __attribute__((aligned(16))) double ldsB[3 * BK * LDT3];     //  49,152 B
+  __shared__ int next_tile;
   const int nct = g.Ncols / BN;
   const int nrt2 = g.M / BM2;
-  const int b = blockIdx.x;
+  int b = blockIdx.x;
+  v2d ra0[4], rb0[2], ra1[4], rb1[2];                    // operand tiles in flight (QUEUE: carried from a tile's epilogue into the next tile)
+  bool primed = false;                                   // QUEUE: k-tiles 0 and 1 of tile b were requested during the previous tile's epilogue
+  auto tile_of = [&](int t, int& rt2_, int& ct_, int& batch_) {   // QUEUE: tile t of the plain launch's dispatch order
+    const int per = nrt2 * nct;
+    batch_ = t / per;
+    const int rem = t - batch_ * per;
+    rt2_ = rem / nct;
+    ct_ = rem - rt2_ * nct;
+  };
+ for (;;) {                                              // (QUEUE: one round per tile; otherwise a single pass)
   int rt2, ct, batch;
-  if (STORE) {                                         // one-dimensional grid, row-tile-major across the WHOLE batch: every output's heaviest
+  if (QUEUE) {
+    tile_of(b, rt2, ct, batch);
+  } else if (STORE) {                                         // one-dimensional grid, row-tile-major across the WHOLE batch: every output's heaviest
     const int per = nct * g.batch;                     // row tiles first (a few hundred workgroups of very unequal length: the order is the packing)
     rt2 = b / per;
     const int rem = b - rt2 * per;
@@ -543,7 +564,6 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_f64_sumsq256x3_kernel(GemmArgs
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = (v4d){0.0, 0.0, 0.0, 0.0};
-  v2d ra0[4], rb0[2], ra1[4], rb1[2];
   const unsigned aoff = (unsigned)(((long)arow * g.lda + sh * 128 + swr * 16 + sl) * 8);      // second element: + 64 rows = 512 B
   const unsigned boff = (unsigned)(((long)brow * g.ldb + bw * 64 + sp * 32 + sl) * 8);        // second element: + 16 columns = 128 B
   const int lda8 = g.lda * 8, ldb8 = g.ldb * 8;        // row strides in bytes (rows + 12 at most inside a tile: 32-bit)
@@ -701,8 +721,10 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_f64_sumsq256x3_kernel(GemmArgs
     k4(ya, yb, 3);
     __syncthreads();
   };
-  fetch(ra0, rb0, A, B);                                  // kend >= 16 k-tiles: the prologue needs no guards
-  fetch(ra1, rb1, A + tileA, B + tileB);
+  if (!(QUEUE && primed)) {
+    fetch(ra0, rb0, A, B);                                // kend >= 16 k-tiles: the prologue needs no guards
+    fetch(ra1, rb1, A + tileA, B + tileB);
+  }
 #pragma unroll
   for (int i = 0; i < 4; ++i) *reinterpret_cast<v2d*>(&ldsA[4 * i * LDA3 + stA]) = ra0[i];
 #pragma unroll
@@ -735,6 +757,8 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_f64_sumsq256x3_kernel(GemmArgs
     step(ra0, rb0, kt + 2 * BK, IC<2>());
     step(ra1, rb1, kt + 3 * BK, IC<0>());
   }
+  int claimed = 0;
+  if (QUEUE && tid == 0) claimed = (int)gridDim.x + atomicAdd(g.tile_ctr, 1);   // the next tile: the round trip runs under the diagonal range
   {
     int cur = rest == 0 ? 0 : (rest == 2 ? 2 : 1);        // the buffer of tile k0
     for (kt = k0; kt < kend; kt += 2 * BK) {
@@ -775,6 +799,8 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_f64_sumsq256x3_kernel(GemmArgs
   // Group q's block i sits in wave row i here: the lane's running sum goes through LDS from wave row to wave row.
   double* xfer = ldsA;                    // [4 (q)][4 (j)][2 (wc)][64 lanes]
   double* red = ldsA + 4 * 4 * 2 * 64;    // [4 (q)][128 cols]
+  int nb = 0;
+  if (QUEUE && tid == 0) next_tile = claimed;
 #pragma unroll 1
   for (int stage = 0; stage < 4; ++stage) {
     if (wr == stage) {
@@ -796,11 +822,35 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_f64_sumsq256x3_kernel(GemmArgs
         }
     }
     __syncthreads();
+    if (QUEUE && stage == 0) {
+      // the next tile is known to every wave: its first two operand tiles are requested now (the staging registers are idle since the
+      // last step) and arrive under the remaining hand-over stages, so the next prologue starts without a memory round trip
+      nb = __builtin_amdgcn_readfirstlane(next_tile);
+      primed = nb < nrt2 * nct * g.batch;
+      if (primed) {
+        int nrt, nc, nz;
+        tile_of(nb, nrt, nc, nz);
+        if (g.rt_desc) nrt = nrt2 - 1 - nrt;
+        const double* An = g.A + (long)nz * g.strideA + (long)nrt * BM2;
+        const double* Bn = g.B + (long)nz * g.strideB + (long)nc * BN;
+        fetch(ra0, rb0, An, Bn);
+        fetch(ra1, rb1, An + tileA, Bn + tileB);
+      }
+    }
   }
   if (tid < 256) {
     const int half = tid >> 7, col = tid & 127;
     double* out = g.sumsq + (long)batch * g.strideSumsq + (long)(rtA + half) * g.Ncols + (long)ct * BN;
     out[col] = red[(2 * half) * 128 + col] + red[(2 * half + 1) * 128 + col];
+  }
+  if (!QUEUE) return;
+  if (!primed) break;
+  b = nb;
+  __syncthreads();                                       // (`red` has been read before the next tile's operands overwrite it)
+ }
+  if (threadIdx.x == 0 && atomicAdd(g.tile_ctr + 1, 1) == (int)gridDim.x - 1) {
+    __hip_atomic_store(g.tile_ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(g.tile_ctr + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -829,7 +879,11 @@ void launch_gemm_f64(const GemmArgs& g0, int batch, int epilogue, hipStream_t s)
 #undef L256
 #endif
       if (g.kb == BM && g.krt == BM && g.kct == 0 && g.K >= g.M) {
-        BOCF_LAUNCH((gemm_tn_f64_sumsq256x3_kernel<0>), grid256, dim3(512), 0, s, g);
+        const long tiles = (long)(g.M / BM2) * nct * batch;
+        if (g.tile_ctr && g.ncu > 0 && tiles <= 0x7fffffffL - g.ncu)     // one workgroup per compute unit over a tile queue (the caller owns the counters)
+          BOCF_LAUNCH((gemm_tn_f64_sumsq256x3_kernel<0, 1>), dim3((unsigned)(tiles < g.ncu ? tiles : g.ncu)), dim3(512), 0, s, g);
+        else
+          BOCF_LAUNCH((gemm_tn_f64_sumsq256x3_kernel<0>), grid256, dim3(512), 0, s, g);
         return;
       }
     }

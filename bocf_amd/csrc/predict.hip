@@ -22,7 +22,8 @@ __device__ __forceinline__ double kern_of_r2_p(int kernel_id, double variance, d
 typedef double v2d_p __attribute__((ext_vector_type(2)));
 typedef float v2f_p __attribute__((ext_vector_type(2)));
 template <int D, int KID, int STORE>
-__global__ __launch_bounds__(256) void cross_kernel(const double* __restrict__ Xs, long strideXs, int N, int Np, int kernel_id_unused,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D <= 8 ? 8 : 1)))
+void cross_kernel(const double* __restrict__ Xs, long strideXs, int N, int Np, int kernel_id_unused,
                                                     const KernHyp* __restrict__ hyp, const double* __restrict__ Xc, int c0, int Cn,
                                                     const double* __restrict__ alpha, double* __restrict__ Kstar, long ldk, long strideK,
                                                     double* __restrict__ meanpart, double* __restrict__ meanlo, int nsplit, int Cpad,
@@ -50,29 +51,82 @@ __global__ __launch_bounds__(256) void cross_kernel(const double* __restrict__ X
   const double* __restrict__ al = alpha + (long)j * Np;
   double* __restrict__ Kj = Kstar + (long)j * strideK;
   float* __restrict__ Kf = reinterpret_cast<float*>(Kstar) + (long)j * strideK;   // fp32 store variant
+  // Full tiles -- every row of the block below N, every column pair of the workgroup below Cn (both tests wave-uniform: all of
+  // them at the headline shape) -- take a loop without the row test and the column selects.  For D <= 8 its scalar operands also run
+  // one row ahead in two named sets: the requests for row kk + 1 are issued once row kk's operands have arrived and are in flight
+  // under row kk's ~90 fp64 instructions, instead of each row waiting for its own two requests (scalar loads return out of order:
+  // every wait is for ALL outstanding ones, so the next request must come after the wait, which the empty asm statements -- they
+  // consume the arrived set and produce the next row index -- make the compiler keep).  Per element the operations and their order are
+  // those of the guarded loop, which keeps the ragged last block / last columns.  The kernel is held at 64 registers (D <= 8): its
+  // grid is one wave per wave slot of the chip, and a form that needs more leaves workgroups behind for a second, uneven round
+  // (measured: +0.15 ... +0.3 ms at the headline shape).
+  const bool full_cols = (int)(blockIdx.x * 512u + 511u) < Cn;
   for (int blk = b0; blk < b1; ++blk) {
     double mean0 = 0.0, mean1 = 0.0, lo0 = 0.0, lo1 = 0.0;
     const int kbeg = blk * BOCF_TILE;
-    for (int kk = kbeg; kk < kbeg + BOCF_TILE; ++kk) {
-      double v0 = 0.0, v1 = 0.0;
-      if (kk < N) {
+    if (full_cols && kbeg + BOCF_TILE <= N) {
+      auto fetch = [&](double (&xr)[D], double& a, int k) {
+#pragma unroll
+        for (int q = 0; q < D; ++q) xr[q] = X[(long)k * D + q];
+        a = al[k];
+      };
+      auto row = [&](const double (&xr)[D], double a, int kk) {
         double r0 = 0.0, r1 = 0.0;
 #pragma unroll
         for (int q = 0; q < D; ++q) {
-          const double xq = X[(long)kk * D + q];
-          const double d0 = xq - xa[q], d1 = xq - xb[q];
+          const double d0 = xr[q] - xa[q], d1 = xr[q] - xb[q];
           r0 += d0 * d0;
           r1 += d1 * d1;
         }
-        v0 = kern_of_r2_p(KID, h.variance, r0);
-        v1 = kern_of_r2_p(KID, h.variance, r1);
-        const double a = al[kk];
+        const double v0 = kern_of_r2_p(KID, h.variance, r0);
+        const double v1 = kern_of_r2_p(KID, h.variance, r1);
         dd_fma_acc(mean0, lo0, v0, a);
         dd_fma_acc(mean1, lo1, v1, a);
+        if (STORE == 1) __builtin_nontemporal_store((v2d_p){v0, v1}, reinterpret_cast<v2d_p*>(Kj + (long)kk * ldk + c));
+        else if (STORE == 2) __builtin_nontemporal_store((v2f_p){(float)v0, (float)v1}, reinterpret_cast<v2f_p*>(Kf + (long)kk * ldk + c));
+      };
+      double xA[D], aA;
+      if constexpr (D <= 8) {
+        double xB[D], aB;
+        fetch(xA, aA, kbeg);
+        for (int kk = kbeg; kk < kbeg + BOCF_TILE; kk += 2) {
+          int kn = kk + 1;
+          asm volatile("" : "+s"(kn) : "s"(xA[0]), "s"(aA));
+          fetch(xB, aB, kn);
+          row(xA, aA, kk);
+          kn = kk + 2 < kbeg + BOCF_TILE ? kk + 2 : kk + 1;    // (the last row of a block asks for itself again: nothing is read beyond the block)
+          asm volatile("" : "+s"(kn) : "s"(xB[0]), "s"(aB));
+          fetch(xA, aA, kn);
+          row(xB, aB, kk + 1);
+        }
+      } else {
+        for (int kk = kbeg; kk < kbeg + BOCF_TILE; ++kk) {
+          fetch(xA, aA, kk);
+          row(xA, aA, kk);
+        }
       }
-      // (non-temporal: K* is gigabytes, read once by the contraction; with plain stores this loop runs a quarter slower -- tools/hbm_kernel_probe.hip)
-      if (STORE == 1) __builtin_nontemporal_store((v2d_p){valid0 ? v0 : 0.0, valid1 ? v1 : 0.0}, reinterpret_cast<v2d_p*>(Kj + (long)kk * ldk + c));
-      else if (STORE == 2) __builtin_nontemporal_store((v2f_p){valid0 ? (float)v0 : 0.f, valid1 ? (float)v1 : 0.f}, reinterpret_cast<v2f_p*>(Kf + (long)kk * ldk + c));
+    } else {
+      for (int kk = kbeg; kk < kbeg + BOCF_TILE; ++kk) {
+        double v0 = 0.0, v1 = 0.0;
+        if (kk < N) {
+          double r0 = 0.0, r1 = 0.0;
+#pragma unroll
+          for (int q = 0; q < D; ++q) {
+            const double xq = X[(long)kk * D + q];
+            const double d0 = xq - xa[q], d1 = xq - xb[q];
+            r0 += d0 * d0;
+            r1 += d1 * d1;
+          }
+          v0 = kern_of_r2_p(KID, h.variance, r0);
+          v1 = kern_of_r2_p(KID, h.variance, r1);
+          const double a = al[kk];
+          dd_fma_acc(mean0, lo0, v0, a);
+          dd_fma_acc(mean1, lo1, v1, a);
+        }
+        // (non-temporal: K* is gigabytes, read once by the contraction; with plain stores this loop runs a quarter slower -- tools/hbm_kernel_probe.hip)
+        if (STORE == 1) __builtin_nontemporal_store((v2d_p){valid0 ? v0 : 0.0, valid1 ? v1 : 0.0}, reinterpret_cast<v2d_p*>(Kj + (long)kk * ldk + c));
+        else if (STORE == 2) __builtin_nontemporal_store((v2f_p){valid0 ? (float)v0 : 0.f, valid1 ? (float)v1 : 0.f}, reinterpret_cast<v2f_p*>(Kf + (long)kk * ldk + c));
+      }
     }
     // (partial means are laid out [block][output of the WHOLE model][column]: a launch that covers a run of outputs writes its slots)
     *reinterpret_cast<v2d_p*>(meanpart + ((long)blk * mtot + jbase + j) * Cpad + c) = (v2d_p){mean0, mean1};
