@@ -63,6 +63,11 @@ SIGNATURES = {
     "bocf_posterior_samples": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p]),
     "bocf_thompson_select": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int, _c_ll_p,
                                             _c_double_p]),
+    "bocf_set_ref_points": (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int]),
+    "bocf_cov_to_ref": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, _c_double_p]),
+    "bocf_conditioned_variance": (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p]),
+    "bocf_acq_kg": (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int,
+                                   _c_double_p, ctypes.c_int, _c_double_p, _c_double_p]),
     "bocf_mean_at_train": (ctypes.c_int, [_ctx_p, _c_double_p]),
     "bocf_acq_linear_grad": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p]),
     "bocf_acq_mc_grad": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p,

@@ -327,3 +327,132 @@ class uPI(_MonteCarlo):
     def __init__(self, *a, **kw):
         super(uPI, self).__init__(*a, **kw)
         self.jitter = 1e-6
+
+
+class uKG(AcquisitionBase):
+    """Discrete composite knowledge gradient: the one-step look-ahead value of x against a set A of reference points,
+
+        KG(x) = sum_l p_l [ (1/Sf) sum_s max_a v(a; x, z_s, theta_l)  -  max_a v0(a; theta_l) ],
+
+    v the posterior expected utility at a after a fantasy observation at x with normals z_s, v0 the current one (the reference's
+    experiment scripts import such acquisitions, test_1a.py:7-8: uKG_SGA / uKG_cf, over the look-ahead helpers of its
+    multi_outputGP, multi_outputGP.py:203-281,309-330).  Everything runs on the device (bocf_acq_kg); the gradient follows the
+    envelope rule.  With a finite number of fantasies KG can be slightly negative; it is not clamped.
+
+    Random numbers, all in the constructor and in this order: Z_samples (n_fantasies, m) and W_samples (25, m) with
+    np.random.normal, then -- without full support -- ten utility parameters (parameter_dist.sample(10)).  The reference points
+    are those of set_reference_points(A); if none are set they are drawn once per model update, at the first evaluation after it:
+    n_ref_points - 1 uniform points in the space's bounds (one np.random.uniform per input dimension) plus the training input with
+    the best current expected utility.  They are staged again whenever the model's fit serial changes.
+
+    The inner expectation follows the recommendation step (recommend.py): the posterior mean for a linear utility, the closed form
+    when the utility's device kind has one, Monte-Carlo over W_samples otherwise.  A utility without a device kind raises
+    NotImplementedError."""
+    analytical_gradient_prediction = True
+
+    def __init__(self, model, space, optimizer=None, cost_withGradients=None, utility=None, n_fantasies=16, n_ref_points=64):
+        self.optimizer = optimizer
+        self.utility = utility
+        super(uKG, self).__init__(model, space, optimizer, cost_withGradients=cost_withGradients)
+        if cost_withGradients is not None:
+            print('LBC acquisition does now make sense with cost. Cost set to constant.')
+        self.cost_withGradients = constant_cost_withGradients
+        if not 1 <= int(n_fantasies) <= 256:
+            raise ValueError("n_fantasies must be in 1 .. 256")
+        if not 1 <= int(n_ref_points) <= 1024:
+            raise ValueError("n_ref_points must be in 1 .. 1024")
+        self.n_attributes = self.model.output_dim
+        self.n_fantasies, self.n_ref_points = int(n_fantasies), int(n_ref_points)
+        self.Z_samples = np.random.normal(size=(self.n_fantasies, self.n_attributes))
+        self.W_samples = np.random.normal(size=(25, self.n_attributes))
+        self.n_hyps_samples = min(10, self.model.number_of_hyps_samples())
+        self.use_full_support = self.utility.parameter_dist.use_full_support
+        if self.use_full_support:
+            self.utility_params_samples = self.utility.parameter_dist.support
+            self.utility_prob_dist = np.atleast_1d(self.utility.parameter_dist.prob_dist)
+        else:
+            self.utility_params_samples = self.utility.parameter_dist.sample(10)
+            self.utility_prob_dist = None
+        self.reference_points = None          # the set in use
+        self._user_reference_points = None
+        self._staged_serial = None
+
+    # ---- what the device evaluates
+    def _mode_and_kind(self):
+        """(mode, device utility kind) as the recommendation step chooses its form (recommend.py)."""
+        from .recommend import _CLOSED_KINDS, _KIND_NAMES
+        m = self.model.output_dim
+        if self.utility.linear:
+            return _ffi.EU_MEAN, _ffi.UTIL_LINEAR
+        try:
+            kind = self.utility.device_kind(m)
+        except NotImplementedError:
+            raise NotImplementedError("uKG needs a utility with a device kind (Utility(..., device=...): linear, neg_sq_dist, neg_sum_exp, "
+                                      "neg_exp_cos, rosenbrock): the look-ahead runs on the device, there is no host loop for a Python callable")
+        name = _KIND_NAMES[kind]
+        if kind == _ffi.UTIL_LINEAR:
+            return _ffi.EU_MEAN, kind
+        if name in _CLOSED_KINDS and not (name == "rosenbrock" and m % 2):
+            return _ffi.EU_CLOSED, kind
+        return _ffi.EU_MC, kind
+
+    def _thetas(self, kind):
+        s = np.asarray(self.utility_params_samples, dtype=float)
+        thetas = s.reshape(len(self.utility_params_samples), -1)
+        if kind in (_ffi.UTIL_NEG_SUM_EXP, _ffi.UTIL_NEG_EXP_COS):
+            thetas = np.zeros((thetas.shape[0], 1))        # parameter unused by these utilities
+        return thetas
+
+    # ---- reference points
+    def set_reference_points(self, A):
+        """Use A (na, d), 1 <= na <= 1024, as the discretisation from now on (None: back to drawn sets)."""
+        self._user_reference_points = None if A is None else np.array(np.atleast_2d(A), dtype=float)
+        self._staged_serial = None
+
+    def _draw_reference_points(self, mode, kind):
+        from .acquisition_optimizer import _bounds_of, samples_multidimensional_uniform
+        model = self._device_model()
+        pts = []
+        if self.n_ref_points > 1:
+            pts.append(np.atleast_2d(samples_multidimensional_uniform(_bounds_of(self.space), self.n_ref_points - 1)))
+        # the training input with the best current expected utility  sum_l p_l E[U(theta_l, f(x))]
+        Xt = np.atleast_2d(model.get_evaluated_points())
+        thetas = self._thetas(kind)
+        L, n = thetas.shape[0], Xt.shape[0]
+        Z = np.broadcast_to(self.W_samples, (L,) + self.W_samples.shape) if mode == _ffi.EU_MC else None
+        v = model.expected_utility(np.tile(Xt, (L, 1)), mode, kind, thetas, np.repeat(np.arange(L), n), Z=Z, n_hyps=self.n_hyps_samples,
+                                   util_params=self.utility.device_params)
+        p = self.utility_prob_dist if self.utility_prob_dist is not None else np.full(L, 1.0 / L)
+        pts.append(Xt[int(np.argmax(np.asarray(p).dot(np.asarray(v).reshape(L, n))))][None, :])
+        return np.concatenate(pts)
+
+    def _stage(self, mode, kind):
+        model = self._device_model()
+        model._ensure_fitted()
+        serial = model._fit_serial
+        if self._staged_serial != serial:
+            self.reference_points = self._user_reference_points if self._user_reference_points is not None else self._draw_reference_points(mode, kind)
+            self._staged_serial = serial
+        model.set_reference_points(self.reference_points)     # (free when this set is the resident one)
+
+    def _device_model(self):
+        if not hasattr(self.model, "acq_kg"):
+            raise TypeError("bocf_amd acquisitions need a bocf_amd.multi_outputGP model (no CPU fallback)")
+        return self.model
+
+    def _evaluate(self, X, grad):
+        X = np.atleast_2d(X)
+        mode, kind = self._mode_and_kind()
+        self._stage(mode, kind)
+        prob = self.utility_prob_dist if self.use_full_support else None
+        out = self._device_model().acq_kg(X, mode, kind, self.utility.device_params, self._thetas(kind), prob, self.Z_samples,
+                                         W=self.W_samples if mode == _ffi.EU_MC else None, n_hyps=self.n_hyps_samples, grad=grad)
+        return X, out
+
+    def _compute_acq(self, X):
+        X, acq = self._evaluate(X, False)
+        return np.reshape(acq, (X.shape[0], 1))
+
+    def _compute_acq_withGradients(self, X):
+        X, (acq, dacq) = self._evaluate(X, True)
+        return np.reshape(acq, (X.shape[0], 1)), np.reshape(dacq, X.shape)

@@ -184,10 +184,24 @@ struct bocf_ctx {
   DevBuf ts_X, ts_K, ts_V, ts_mp, ts_mu, ts_Z, ts_jit, ts_u, ts_theta, ts_params, ts_out;
   std::vector<DevBuf> ts_F;  // resident samples of hyper-sample h: (m / H, C, ts_S[h]) -- ts_S[h] = 0: none
   std::vector<int> ts_S;
+  // ---- look-ahead posterior and knowledge gradient (capi_kg.hip): the resident reference set A of all m outputs -- V_A = R^T K(X, A) and
+  // Wa = Ky^-1 K(X, A) (Np x nap each, nap = na rounded up to 128), mu(A), the raw sigma^2(A) (m x nap each), the conditioning nugget
+  // noise + 1e-8 + jitter per output -- and the per-chunk workspaces.  Buffers of their own: the predict, acquisition, expected-utility and
+  // Thompson state is left as it was (scratch shared with the joint posterior: ts_K, ts_mp)
+  int kg_na = 0;             // reference points resident (0 = none)
+  DevBuf kg_XA, kg_VA, kg_Wa, kg_muA, kg_s2A, kg_nug;
+  DevBuf kg_V, kg_W, kg_cov, kg_s2c, kg_dcov, kg_dmean, kg_dvar, kg_par, kg_v0, kg_astar, kg_AB, kg_out, kg_dout;
 };
 
 // the resident Thompson samples belong to one posterior and one candidate set: dropped by every fit, data change and candidate upload
 void bocf_thompson_drop(bocf_ctx* c);
+// the resident reference set belongs to one posterior: dropped by every fit and data change (NOT by a candidate upload)
+void bocf_kg_drop(bocf_ctx* c);
+// capi_thompson.hip, shared with capi_kg.hip: the argument checks of the joint-posterior entry points (errors name `who`) and
+// V = R^T K(X, Xq) for the mg outputs from j0 (Np x npad per output, k-major) with, for mu != nullptr, the posterior mean at Xq (mg x npad)
+int bocf_check_posterior(bocf_ctx* c, const char* who);
+int bocf_group_range(bocf_ctx* c, const char* who, int group, int* j0, int* mg, int* per);
+int bocf_enqueue_V(bocf_ctx* c, int j0, int mg, const double* Xq, int n, int npad, double* V, double* mu);
 
 
 // HIP-event bracket of a named phase on the context's stream (only with option "profile" = 1; otherwise free)

@@ -365,3 +365,46 @@ void launch_post_sample(const double* U, long ldu, long strideU, const double* Z
 // u[s][c] = U(theta_s, F[:, c, s]) (utility_dev.h) for one sample block F (m, C, S)
 void launch_thompson_util(const double* F, int m, int C, int S, int util_kind, const double* theta, int theta_dim, const double* params, double* u,
                           long ldu, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------
+// look-ahead posterior and discrete composite knowledge gradient (kg.hip)
+// ---------------------------------------------------------------------------------------
+// out[j][c] = variance_j - sum_{kk < K} V[j][kk][c]^2 for c < n: the raw (noiseless, unclipped) posterior variance from V = R^T K(X, x_c)
+void launch_kg_diag(const double* V, long ldv, long strideV, int K, int n, const KernHyp* hyp, double* out, long ldo, int m, hipStream_t s);
+// out[j][c][a - a0][q] = d Sigma_j(a, x_c) / d x_cq for the Cn candidates Xc and the reference points a0 <= a < a0 + an of XA:
+//   dk_j(x_c, a)/dx - sum_i dk_j(x_c, X_i)/dx Wa[j][i][a]   (gp.py:602-610), Wa = Ky^-1 K(X, A) (Np x ldw per output); i in increasing order
+void launch_cov_grad(const double* Xs, long strideXs, int N, int d, int kernel_id, const int* kids, const KernHyp* hyp, const double* Xc, int Cn,
+                     const double* XA, int a0, int an, const double* Wa, long ldw, long strideW, double* out, int m, hipStream_t s);
+// conditioned on reference point q:  var[j][c] = s2c[j][c] - cov[j][c][q]^2 / s2(q),  s2(q) = max(s2A[j][q], 0) + nug[j]   (gp.py:543, raw);
+// dvar[j][c][:] = ds2c[j][c][:] - 2 cov[j][c][q] dcov[j][c][:] / s2(q)  (dvar = nullptr: values only).  var (m, C), dvar (m, C, d) contiguous.
+void launch_cond_var(const double* cov, long ldc, long strideC, int q, const double* s2c, long lds, const double* s2A, long lda, const double* nug,
+                     const double* ds2c, long ldg, const double* dcov, int C, int d, double* var, double* dvar, int m, hipStream_t s);
+struct KgArgs {
+  const double* cov; int ldc; long strideC;         // Sigma_j(x_c, a): (m, rows, ldc) of one hyper-sample, C x na valid
+  const double* s2c; int lds;                       // raw sigma^2_j(x_c): (m, lds)
+  const double* nug;                                // (m): noise_j + 1e-8 + jitter_j
+  const double* muA; const double* s2A; int lda;    // (m, lda): mu_j(a) and the raw sigma^2_j(a)
+  const double* v0;                                 // (L): max_a v0(a; theta_l) of this hyper-sample (launch_kg_v0)
+  const double* Zf; int Sf;                         // (Sf, m) fantasy normals
+  const double* theta; int theta_dim; const double* prob; int L;
+  const double* util_params;                        // (BOCF_MAX_M)
+  const double* Wt; int S;                          // (m, S) transposed common random numbers (MC mode)
+  int m, na, C, mode, util_kind;
+  double* acq; int accumulate; double scale;        // (C): written, or added to (hyper-sample h > 0)
+  int* astar; double* AB;                           // gradient form: the maximiser (C, L, Sf) and dv/dmu | dv/dvar at it (C, L, Sf, 2 m); else nullptr
+};                                                  // (launch_kg writes astar, launch_kg_partials reads it and writes AB)
+// bytes of LDS the tables of a launch need; the launcher keeps them in LDS when they fit in 64 KiB, else the kernel reads them from memory
+size_t kg_table_bytes(const KgArgs& a);
+void launch_kg(const KgArgs& a, hipStream_t s);
+void launch_kg_v0(const KgArgs& a, double* v0_out, hipStream_t s);
+void launch_kg_partials(const KgArgs& a, hipStream_t s);
+struct KgGradArgs {
+  const double* cov; long ldc; long strideC;        // as KgArgs
+  const double* dcov;                               // (m, C, na, d)
+  const double* s2c; long lds; const double* ds2c; long ldg;   // raw sigma^2_j(x_c) and its input gradient (m, ldg, d)
+  const double* nug; const double* Zf; int Sf; const double* prob; int L;
+  int m, na, C, d;
+  const int* astar; const double* AB;
+  double* dacq; int accumulate; double scale;       // (C, d)
+};
+void launch_kg_grad(const KgGradArgs& a, hipStream_t s);

@@ -108,7 +108,9 @@ extern "C" void bocf_destroy(bocf_ctx* c) {
                     &c->info, &c->mu_train, &c->rvec, &c->dvec, &c->hmc_buf, &c->Xc, &c->Kstar, &c->meanpart, &c->sumsq, &c->mean, &c->var, &c->acq, &c->Vbuf, &c->dmean, &c->dvar, &c->dacq, &c->Vs, &c->Ws, &c->theta,
                     &c->prob, &c->best, &c->params, &c->Wt, &c->blk_idx, &c->blk_val, &c->out_idx, &c->out_val, &c->gpart, &c->gout, &c->pack, &c->gidx,
                     &c->gval, &c->shard_meta, &c->chol_flags, &c->eu_theta, &c->eu_rows, &c->eu_Z, &c->eu_val, &c->eu_grad,
-                    &c->ts_X, &c->ts_K, &c->ts_V, &c->ts_mp, &c->ts_mu, &c->ts_Z, &c->ts_jit, &c->ts_u, &c->ts_theta, &c->ts_params, &c->ts_out};
+                    &c->ts_X, &c->ts_K, &c->ts_V, &c->ts_mp, &c->ts_mu, &c->ts_Z, &c->ts_jit, &c->ts_u, &c->ts_theta, &c->ts_params, &c->ts_out,
+                    &c->kg_XA, &c->kg_VA, &c->kg_Wa, &c->kg_muA, &c->kg_s2A, &c->kg_nug, &c->kg_V, &c->kg_W, &c->kg_cov, &c->kg_s2c, &c->kg_dcov, &c->kg_dmean, &c->kg_dvar,
+                    &c->kg_par, &c->kg_v0, &c->kg_astar, &c->kg_AB, &c->kg_out, &c->kg_dout};
   for (DevBuf* b : bufs) b->release();
   if (c->infer_out) (void)hipHostFree(c->infer_out);
   if (c->tile_ctr) (void)hipFree(c->tile_ctr);
@@ -252,6 +254,7 @@ extern "C" int bocf_set_posterior(bocf_ctx* c, int m, int C, int N, const double
   HIPCHK(hipStreamSynchronize(c->stream));
   c->m = m; c->N = N; c->Np = round_up(N, BOCF_TILE); c->d = 1; c->C = C; c->pred_cap = cap;
   bocf_thompson_drop(c);
+  bocf_kg_drop(c);
   c->fitted = true;
   c->canned = true;
   c->have_acq = false;

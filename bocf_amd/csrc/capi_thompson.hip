@@ -11,7 +11,7 @@ void bocf_thompson_drop(bocf_ctx* c) {
 }
 
 // the outputs `group` selects: hyper-sample h's [h m', (h + 1) m') (m' = outputs per hyper-sample), or all of them for -1
-static int group_range(bocf_ctx* c, const char* who, int group, int* j0, int* mg, int* per) {
+int bocf_group_range(bocf_ctx* c, const char* who, int group, int* j0, int* mg, int* per) {
   const int H = c->hyper_samples > 0 ? c->hyper_samples : 1;
   if (c->m % H) return fail(who, "the fitted outputs are not a whole number of hyper-samples (option hyper_samples)");
   *per = c->m / H;
@@ -26,7 +26,7 @@ static int group_range(bocf_ctx* c, const char* who, int group, int* j0, int* mg
   return 0;
 }
 
-static int check_posterior(bocf_ctx* c, const char* who) {
+int bocf_check_posterior(bocf_ctx* c, const char* who) {
   if (!c || !c->fitted) return fail(who, "model not fitted");
   if (c->canned) return fail(who, "the context holds a host-given posterior (bocf_set_posterior): it has no factor to sample from; fit first");
   return 0;
@@ -39,7 +39,7 @@ static int check_workspace(bocf_ctx* c, const char* who, int mg, long rows, long
 }
 
 // V = R^T K(X, Xq) for the mg outputs from j0 (Np x npad per output, k-major) and, with mu != nullptr, the posterior mean at Xq (mg x npad)
-static int enqueue_V(bocf_ctx* c, int j0, int mg, const double* Xq, int n, int npad, double* V, double* mu) {
+int bocf_enqueue_V(bocf_ctx* c, int j0, int mg, const double* Xq, int n, int npad, double* V, double* mu) {
   const int N = c->N, Np = c->Np, nrt = Np / BOCF_TILE;
   const long strideS = (long)Np * Np;
   const size_t plane = (size_t)mg * nrt * npad;
@@ -61,11 +61,11 @@ static int enqueue_V(bocf_ctx* c, int j0, int mg, const double* Xq, int n, int n
 
 extern "C" int bocf_posterior_cov(bocf_ctx* c, const double* X1, int n1, const double* X2, int n2, int group, double* cov_out) {
   static const char* who = "bocf_posterior_cov";
-  if (check_posterior(c, who)) return -1;
+  if (bocf_check_posterior(c, who)) return -1;
   if (!X1 || !X2 || !cov_out) return fail(who, "null argument");
   if (n1 < 1 || n2 < 1) return fail(who, "n1 and n2 must be >= 1");
   int j0, mg, per;
-  if (group_range(c, who, group, &j0, &mg, &per)) return -1;
+  if (bocf_group_range(c, who, group, &j0, &mg, &per)) return -1;
   const int d = c->d, Np = c->Np;
   const int n1p = round_up(n1, BOCF_TILE), n2p = round_up(n2, BOCF_TILE);
   if (check_workspace(c, who, mg, n1p, n2p)) return -1;
@@ -81,7 +81,7 @@ extern "C" int bocf_posterior_cov(bocf_ctx* c, const double* X1, int n1, const d
   HIPCHK(hipMemcpyAsync(x2, X2, sizeof(double) * (size_t)n2 * d, hipMemcpyHostToDevice, c->stream));
   {
     PhaseTimer t(c, "post_cov");
-    if (enqueue_V(c, j0, mg, x1, n1, n1p, V1, nullptr) || enqueue_V(c, j0, mg, x2, n2, n2p, V2, nullptr)) return -1;
+    if (bocf_enqueue_V(c, j0, mg, x1, n1, n1p, V1, nullptr) || bocf_enqueue_V(c, j0, mg, x2, n2, n2p, V2, nullptr)) return -1;
     const int* kids = BOCF_KIDS(c);
     launch_post_cov(V1, n1p, (long)Np * n1p, V2, n2p, (long)Np * n2p, x1, n1, x2, n2, d, Np, c->kernel_id, kids ? kids + j0 : nullptr,
                     c->hypd.as<KernHyp>() + j0, nullptr, 0, c->ts_out.as<double>(), n2p, (long)n1p * n2p, mg, c->stream);
@@ -117,13 +117,13 @@ struct BorrowStream {
 
 extern "C" int bocf_posterior_samples(bocf_ctx* c, int group, const double* Z, int S, int max_jitter_tries, double* samples_out, double* jitter_out) {
   static const char* who = "bocf_posterior_samples";
-  if (check_posterior(c, who)) return -1;
+  if (bocf_check_posterior(c, who)) return -1;
   if (!Z) return fail(who, "null Z");
   if (S < 1 || S > 256) return fail(who, "S out of range (1 .. 256)");
   const int C = c->C;
   if (C < 1) return fail(who, "no resident candidates (bocf_set_candidates)");
   int j0, mg, per;
-  if (group_range(c, who, group, &j0, &mg, &per)) return -1;
+  if (bocf_group_range(c, who, group, &j0, &mg, &per)) return -1;
   const int H = c->m / per, h0 = group < 0 ? 0 : group, h1 = group < 0 ? H : group + 1;
   const int d = c->d, Np = c->Np, Cp = round_up(C, BOCF_TILE), nbc = Cp / BOCF_TILE;
   const long strideS = (long)Cp * Cp;
@@ -158,7 +158,7 @@ extern "C" int bocf_posterior_samples(bocf_ctx* c, int group, const double* Z, i
   };
   {
     PhaseTimer t(c, "post_cov");
-    if (enqueue_V(c, j0, mg, c->Xc.as<double>(), C, Cp, c->ts_V.as<double>(), c->ts_mu.as<double>())) return -1;
+    if (bocf_enqueue_V(c, j0, mg, c->Xc.as<double>(), C, Cp, c->ts_V.as<double>(), c->ts_mu.as<double>())) return -1;
   }
   build(false);
   // rung 0 from the mean of each Sigma_j's diagonal
@@ -229,7 +229,7 @@ extern "C" int bocf_posterior_samples(bocf_ctx* c, int group, const double* Z, i
 extern "C" int bocf_thompson_select(bocf_ctx* c, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim, int k,
                                     long long* idx_out, double* val_out) {
   static const char* who = "bocf_thompson_select";
-  if (check_posterior(c, who)) return -1;
+  if (bocf_check_posterior(c, who)) return -1;
   int P = 0;
   for (int s : c->ts_S) P += s;
   if (P == 0) return fail(who, "no resident samples: call bocf_posterior_samples first");

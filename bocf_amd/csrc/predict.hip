@@ -2,6 +2,7 @@
 // small finalisation kernels.  The N^2 C contraction itself is gemm_f64.hip.
 #include "bocf_internal.h"
 #include "../../include/bocf_hip.h"
+#include "kern_grad_dev.h"
 
 __device__ __forceinline__ double kern_of_r2_p(int kernel_id, double variance, double r2) {
   if (kernel_id <= 1) return variance * bocf_exp_nonpos(-0.5 * r2);
@@ -306,16 +307,6 @@ void launch_finalize_var(const double* sumsq, int nrt, int Cpad, const KernHyp* 
 // with dk/dx_q = f(r) (x_q - X_iq) / l_q^2, f = invdist * dK_dr (stationary.py:312-331, se.py:135-148):
 //   RBF/SE  -k(r);   Matern52  -(5/3) s2 (1 + sqrt5 r) e^{-sqrt5 r};   Matern32  -3 s2 e^{-sqrt3 r}.
 // One workgroup per (candidate, output); lanes stride the training points; fixed-order reduction.
-__device__ __forceinline__ double kern_dfac(int kernel_id, double variance, double r2) {
-  if (kernel_id <= 1) return -variance * bocf_exp_nonpos(-0.5 * r2);
-  const double r = sqrt(r2);
-  if (kernel_id == 2) {
-    const double s5r = 2.23606797749978969641 * r;
-    return -(5.0 / 3.0) * variance * (1.0 + s5r) * bocf_exp_nonpos(-s5r);
-  }
-  return -3.0 * variance * bocf_exp_nonpos(-1.73205080756887729353 * r);
-}
-
 template <int D>
 __global__ __launch_bounds__(256) void grad_kernel(const double* __restrict__ Xs, long strideXs, int N, int Np, int kernel_id,
                                                    const KernHyp* __restrict__ hyp, const double* __restrict__ Xc, int c0,

@@ -120,6 +120,8 @@ class multi_outputGP(object):
         self._fit_key = None
         self._W_key = None
         self._Z_key = None
+        self._ref_key = None          # reference set resident on the device (set_reference_points)
+        self._cov_points = self._next_point = self._grad_point = None
         self.incremental = True       # O(N^2) updateModel when only targets change or one observation is appended
         # ---- hyper-parameter learning (fixed_hyps=False): GPModel's sampler settings (gpmodel.py:32)
         self.n_burnin, self.subsample_interval, self.step_size, self.leapfrog_steps, self.max_iters = 100, 10, 1e-1, 20, 200
@@ -155,6 +157,7 @@ class multi_outputGP(object):
         st["_n_resident"] = None
         st["_W_key"] = None
         st["_Z_key"] = None
+        st["_ref_key"] = None
         st["_query_cache"] = st["_grad_cache"] = None
         st["_ibuf"] = None
         return st
@@ -187,6 +190,7 @@ class multi_outputGP(object):
             raise ValueError("Y_all must hold output_dim arrays of N observations")
         prevX = self._X
         self._n_resident = None
+        self._ref_key = None          # every model change drops the device's reference set
         self._X, self._Y = X.copy(), [y[:, None].copy() for y in Y]
         self._Ymat = None
         self._ibuf = None
@@ -201,12 +205,14 @@ class multi_outputGP(object):
             if X.shape == prevX.shape and np.array_equal(X, prevX):
                 _ffi.check(lib.bocf_update_targets(ctx.handle, _ffi.dptr(Ymat), _ffi.dptr(lml)), "bocf_update_targets")
                 self.log_marginal = lml
+                self._fit_serial += 1
                 return
             if X.shape[0] == prevX.shape[0] + 1 and X.shape[1] == prevX.shape[1] and np.array_equal(X[:-1], prevX):
                 xnew = _ffi.f64(X[-1])
                 rc = _ffi.check(lib.bocf_append(ctx.handle, _ffi.dptr(xnew), _ffi.dptr(Ymat), _ffi.dptr(lml)), "bocf_append")
                 if rc == 0:
                     self.log_marginal = lml
+                    self._fit_serial += 1
                     return
         self._fit()
 
@@ -574,18 +580,151 @@ class multi_outputGP(object):
         """d var / dX, (m, n, d)  (multi_outputGP.py:297-306 -> gp.py:464-490)."""
         return self._gradients(X)[1]
 
-    # ---- reference methods with no caller on the path (multi_outputGP.py:204-281,309-330: knowledge-gradient style
-    # look-ahead helpers that cbo.py and the EI/PI acquisitions never reach): named so that a script using them fails
-    # with a clear message instead of an AttributeError
+    # ---- look-ahead posterior (multi_outputGP.py:203-281,309-330 -> GPy/core/gp.py:493-627): covariance against a staged point set,
+    # variance conditioned on a next point, gradients of the posterior covariance -- what the knowledge-gradient acquisitions are built
+    # from (bocf_amd.uKG).  All act on the current hyper-sample, like posterior_covariance_between_points.  The device keeps ONE resident
+    # reference set; the set a method needs is staged when it differs from the resident one (keyed like set_mc_samples), so the three
+    # "partial precomputations" can be interleaved freely.  Two deliberate differences from the reference's array shapes: the
+    # covariance-gradient methods are defined for every kernel family (the reference's only work for its SE kernel), and they take ONE
+    # point x2 (1, d) -- the only case in which the reference's (m, n, d) result is defined.
     def _off_path(self, *a, **kw):
         raise NotImplementedError("not part of the accelerated path: cbo.py and the maEI/maPI/uEI_noiseless/uPI/EI/PI acquisitions never "
                                   "call it (SURVEY.md section 8b)")
 
-    partial_precomputation_for_covariance = partial_precomputation_for_covariance_gradient = _off_path
-    partial_precomputation_for_variance_conditioned_on_next_point = posterior_variance_conditioned_on_next_point = _off_path
-    posterior_variance_gradient_conditioned_on_next_point = _off_path
-    posterior_covariance_between_points_partially_precomputed = posterior_covariance_gradient = _off_path
-    posterior_covariance_gradient_partially_precomputed = _off_path
+    def _points(self, X, what):
+        if self._X is None:
+            raise RuntimeError("updateModel has not been called")
+        X = _ffi.f64(np.atleast_2d(X))
+        if X.ndim != 2 or X.shape[1] != self._X.shape[1]:
+            raise ValueError("%s must be (n, %d)" % (what, self._X.shape[1]))
+        return X
+
+    def set_reference_points(self, A):
+        """Stage the reference set A (na, d), 1 <= na <= 1024, on the device for ALL hyper-samples (bocf_set_ref_points): V_A, Ky^-1 K(X, A),
+        mu(A), sigma^2(A).  It stays resident until it is replaced or the model changes; re-sending the resident set is free."""
+        self._ensure_fitted()
+        A = self._points(A, "the reference points")
+        key = (A.shape, hash(A.tobytes()), self._fit_serial)
+        if key == getattr(self, "_ref_key", None):
+            return
+        self._ref_key = None
+        _ffi.check(_ffi.load().bocf_set_ref_points(self._context().handle, _ffi.dptr(A), A.shape[0]), "bocf_set_ref_points")
+        self._ref_key = key
+
+    def _staged(self, name, what):
+        P = getattr(self, name, None)
+        if P is None:
+            raise RuntimeError("%s has not been called" % what)
+        return P
+
+    def partial_precomputation_for_covariance(self, X):
+        """multi_outputGP.py:203-210 -> gp.py:547-561: X (n2, d) becomes the precomputed point set."""
+        self._cov_points = self._points(X, "X").copy()
+        self.set_reference_points(self._cov_points)
+
+    def posterior_covariance_between_points_partially_precomputed(self, X1, X2):
+        """Noiseless, unclipped posterior covariance between X1 (n1, d) and the precomputed set X2, (m, n1, n2)
+        (multi_outputGP.py:269-281 -> gp.py:564-573).  X2 must be the set given to partial_precomputation_for_covariance."""
+        X2 = self._points(X2, "X2")
+        P = self._staged("_cov_points", "partial_precomputation_for_covariance")
+        if X2.shape != P.shape or not np.array_equal(X2, P):
+            raise ValueError("X2 is not the point set given to partial_precomputation_for_covariance")
+        return self._cov_to_ref(X1, P, grad=False)[0]
+
+    def _cov_to_ref(self, X, A, grad):
+        """(Sigma(X, A) (m, n, na), d Sigma(X_i, a) / d X_i (m, n, na, d) or None) for the current hyper-sample."""
+        self._ensure_fitted()
+        X = self._points(X, "X")
+        self.set_reference_points(A)
+        n = self._set_candidates(X)
+        na, d = A.shape
+        cov = np.empty((self.output_dim, n, na))
+        dcov = np.empty((self.output_dim, n, na, d)) if grad else None
+        if n:
+            _ffi.check(_ffi.load().bocf_cov_to_ref(self._context().handle, self._group(), _ffi.dptr(cov), _ffi.dptr(dcov)), "bocf_cov_to_ref")
+        return cov, dcov
+
+    def partial_precomputation_for_variance_conditioned_on_next_point(self, next_point):
+        """multi_outputGP.py:223-230 -> gp.py:493-511: stages the next point (1, d)."""
+        P = self._points(next_point, "next_point")
+        if P.shape[0] != 1:
+            raise ValueError("next_point must be one point (1, d)")
+        self._next_point = P.copy()
+
+    def _conditioned(self, X, grad):
+        self._ensure_fitted()
+        P = self._staged("_next_point", "partial_precomputation_for_variance_conditioned_on_next_point")
+        X = self._points(X, "X")
+        self.set_reference_points(P)
+        n = self._set_candidates(X)
+        var = np.empty((self.output_dim, n))
+        dvar = np.empty((self.output_dim, n, X.shape[1])) if grad else None
+        if n:
+            _ffi.check(_ffi.load().bocf_conditioned_variance(self._context().handle, self._group(), 0, _ffi.dptr(var), _ffi.dptr(dvar)),
+                       "bocf_conditioned_variance")
+        return var, dvar
+
+    def posterior_variance_conditioned_on_next_point(self, X):
+        """Variance at X (n, d) once the staged next point has been observed, (m, n): sigma^2(X) - Sigma(X, x)^2 / (max(sigma^2(x), 0) +
+        noise + 1e-8 + jitter), raw -- no clip, no noise (multi_outputGP.py:233-242 -> gp.py:514-544, which factorizes the bordered Ky)."""
+        return self._conditioned(X, False)[0]
+
+    def posterior_variance_gradient_conditioned_on_next_point(self, X):
+        """Its gradient in X, (m, n, d) (multi_outputGP.py:245-254)."""
+        return self._conditioned(X, True)[1]
+
+    def posterior_covariance_gradient(self, X, x2):
+        """d Sigma(X_i, x2) / d X_i for ONE point x2 (1, d), (m, n, d) (multi_outputGP.py:309-318 -> gp.py:586-610)."""
+        P = self._points(x2, "x2")
+        if P.shape[0] != 1:
+            raise ValueError("x2 must be one point (1, d)")
+        return self._cov_to_ref(X, P, grad=True)[1][:, :, 0, :].copy()
+
+    def partial_precomputation_for_covariance_gradient(self, x):
+        """multi_outputGP.py:213-220 -> gp.py:613-618: stages the point x (1, d) of the next method."""
+        P = self._points(x, "x")
+        if P.shape[0] != 1:
+            raise ValueError("x must be one point (1, d)")
+        self._grad_point = P.copy()
+
+    def posterior_covariance_gradient_partially_precomputed(self, X, x2):
+        """As posterior_covariance_gradient, for the point staged by partial_precomputation_for_covariance_gradient
+        (multi_outputGP.py:321-330 -> gp.py:621-627)."""
+        P = self._staged("_grad_point", "partial_precomputation_for_covariance_gradient")
+        x2 = self._points(x2, "x2")
+        if x2.shape != P.shape or not np.array_equal(x2, P):
+            raise ValueError("x2 is not the point given to partial_precomputation_for_covariance_gradient")
+        return self._cov_to_ref(X, P, grad=True)[1][:, :, 0, :].copy()
+
+    def acq_kg(self, X, mode, util_kind, util_params, thetas, prob, Zf, W=None, n_hyps=None, grad=False, fetch=True):
+        """Discrete composite knowledge gradient of the batch X (n, d) against the resident reference set (bocf_acq_kg): `mode` "mean",
+        "closed" or "mc" (or the _ffi.EU_* value) is the inner expectation, Zf (Sf, m) the fantasy normals, W (S, m) the common random
+        numbers of the "mc" mode.  Returns KG (n,), or (KG (n,), dKG/dX (n, d)) with grad=True.  The values stay on the device for
+        select_topk (fetch=False returns None)."""
+        modes = {"mean": _ffi.EU_MEAN, "closed": _ffi.EU_CLOSED, "mc": _ffi.EU_MC}
+        mode = modes[mode] if isinstance(mode, str) else int(mode)
+        self._begin_acq(n_hyps, True)
+        if getattr(self, "_ref_key", None) is None or self._ref_key[2] != self._fit_serial:
+            raise RuntimeError("no reference points resident for this fit: call set_reference_points")
+        if mode == _ffi.EU_MC:
+            if W is None:
+                raise ValueError("the Monte-Carlo mode needs W (S, output_dim)")
+            self.set_mc_samples(W)
+        n = self._set_candidates(np.atleast_2d(X))
+        Zf = _ffi.f64(np.atleast_2d(Zf))
+        if Zf.shape[1] != self.output_dim:
+            raise ValueError("Zf must be (Sf, output_dim)")
+        th = _ffi.f64(np.atleast_2d(thetas))
+        L, tdim = th.shape
+        params = None if util_params is None else _ffi.f64(np.atleast_1d(util_params))
+        prob = None if prob is None else _ffi.f64(np.atleast_1d(prob))
+        acq = np.empty(n) if fetch else None
+        dacq = np.empty((n, self._X.shape[1])) if grad else None
+        if n:
+            _ffi.check(_ffi.load().bocf_acq_kg(self._context().handle, mode, int(util_kind), _ffi.dptr(params), 0 if params is None else params.size,
+                                               _ffi.dptr(th), tdim, _ffi.dptr(prob), L, _ffi.dptr(Zf), Zf.shape[0], _ffi.dptr(acq), _ffi.dptr(dacq)),
+                       "bocf_acq_kg")
+        return (acq, dacq) if grad else acq
 
     # ---- joint posterior and composite Thompson sampling ------------------------------------------------------------------------
     def _group(self):

@@ -334,6 +334,51 @@ int bocf_set_eu_samples(bocf_ctx* ctx, const double* Z, int L, int S);
 int bocf_expected_utility(bocf_ctx* ctx, int mode, int util_kind, const double* util_params, int n_util_params, const double* theta,
                           int theta_dim, int L, const int* row_param, int n_hyps, double* val_out, double* grad_out);
 
+/* ---- look-ahead posterior and the discrete composite knowledge gradient.  The reference's multi_outputGP carries look-ahead helpers
+ * (multi_outputGP.py:203-281,309-330 -> GPy/core/gp.py:493-627) for the knowledge-gradient acquisitions its experiment scripts import
+ * (test_1a.py:7-8).  Per output j, with the fit's own Ky_j = K_j + (noise_j + 1e-8 + jitter_j) I, mu_j and sigma^2_j the posterior mean and
+ * the noiseless, unclipped variance, Sigma_j(a, x) = k_j(a, x) - k_j(a, X) Ky_j^-1 k_j(X, x):
+ *   s2_j(x)         = max(sigma^2_j(x), 0) + noise_j + 1e-8 + jitter_j
+ *   sigma^2_j(a | x) = sigma^2_j(a) - Sigma_j(a, x)^2 / s2_j(x)       raw: no clip, no noise (gp.py:514-544 factorizes the bordered Ky with
+ *                                                                    N + 1 rows; by the Schur complement that is this rank-one downdate)
+ *   beta_j(a; x)    = Sigma_j(a, x) / s_j(x),   mu_j(a | x, z) = mu_j(a) + beta_j(a; x) z_j     (fantasy with a standard normal z_j)
+ * These entry points work on a fitted model (not a host-given posterior), are local to the context, use fp64 throughout (options
+ * predict_f32 / predict_i8 are not read) and leave the predict, acquisition-parameter, Monte-Carlo-sample, expected-utility, best-so-far
+ * and Thompson state as it was; only the acquisition call overwrites the acquisition vector, as every acquisition does.  Every failure
+ * returns < 0 with the entry point's name in the error text; the context stays usable.  M = all fitted outputs, `group` and M_g as for
+ * the joint posterior above.
+ *
+ * bocf_set_ref_points: stages the reference set A = Xa (na, d), 1 <= na <= 1024, for all M outputs: V_A = R^T K(X, A), Wa = Ky^-1 K(X, A),
+ *   mu(A) and sigma^2(A) (multi_outputGP.partial_precomputation_for_covariance, multi_outputGP.py:245-254 -> gp.py:547-561).  It stays
+ *   resident until it is replaced; a fit, an appended observation, new targets or a host-given posterior drop it, a new candidate set does
+ *   not.  2 M Np nap 8 bytes (nap = na rounded up to 128) must fit in option "workspace_mb".
+ * bocf_cov_to_ref: cov_out[j][c][a] = Sigma_j(x_c, a) for the resident candidates, (M_g, C, na), as V_c^T V_A subtracted from k
+ *   (posterior_covariance_between_points_partially_precomputed, multi_outputGP.py:269-281 -> gp.py:564-573); dcov_out (M_g, C, na, d) or
+ *   NULL: d Sigma_j(x_c, a) / d x_c = dk_j(x_c, a)/dx - sum_i dk_j(x_c, X_i)/dx Wa[i][a] (posterior_covariance_gradient and its
+ *   precomputed twin, multi_outputGP.py:309-330 -> gp.py:586-627), for every kernel family.  The candidates are worked off in chunks whose V
+ *   fits in "workspace_mb"; the gradient form needs M_g C na d 8 bytes there.
+ * bocf_conditioned_variance: var_out[j][c] = sigma^2_j(x_c | a_q), the variance at the resident candidates conditioned on reference
+ *   point q, (M_g, C) (posterior_variance_conditioned_on_next_point, multi_outputGP.py:215-228 -> gp.py:514-544); dvar_out (M_g, C, d) or
+ *   NULL: its gradient in x_c, d sigma^2_j(x_c)/dx - 2 Sigma d Sigma/dx / s2_j(a_q) (multi_outputGP.py:231-242).
+ * bocf_acq_kg: the one-step look-ahead value of every resident candidate against the discretisation A,
+ *     KG(x) = sum_l p_l [ (1/Sf) sum_s max_a v(a; x, z_s, theta_l) - max_a v0(a; theta_l) ],
+ *     v(a; x, z, theta) = E_w[ U(theta, mu(a | x, z) + sigma(a | x) o w) ]  with sigma^2(a | x) clipped at 1e-10, v0 the same with the
+ *     current mu(a), sigma^2(a); ties in max_a go to the lowest a.  `mode` is the inner expectation, as for the expected utility:
+ *     BOCF_EU_MEAN theta . mu, BOCF_EU_CLOSED the closed forms (an error for LINEAR and NEG_EXP_COS), BOCF_EU_MC the MEAN over the S <= 256
+ *     common random numbers of the Monte-Carlo samples set for the acquisitions.  theta (L, theta_dim), prob (L) or NULL (= 1 / L),
+ *     Zf (Sf, m) fantasy normals, 1 <= Sf <= 256.  With a finite Sf the value can be slightly negative; it is not clamped.  acq_out (C) or
+ *     NULL; the values stay in the acquisition vector for the top-k selection (larger is better).  With option hyper_samples = H the
+ *     first acq_hyper_samples are averaged.  dacq_out (C, d) or NULL: the envelope-rule gradient (the maximiser a* of every (s, l) held
+ *     fixed); this form holds d Sigma / dx of every (output, candidate, reference point) at once -- averaged outputs x C na d 8 bytes
+ *     within "workspace_mb" -- and is meant for the optimiser's small batches.
+ *     (The reference's own knowledge-gradient acquisitions, uKG_SGA / uKG_cf of test_1a.py:7-8, are not in its tree; this is the
+ *     discrete form over its look-ahead helpers gp.py:493-627.) */
+int bocf_set_ref_points(bocf_ctx* ctx, const double* Xa, int na);
+int bocf_cov_to_ref(bocf_ctx* ctx, int group, double* cov_out, double* dcov_out);
+int bocf_conditioned_variance(bocf_ctx* ctx, int group, int q, double* var_out, double* dvar_out);
+int bocf_acq_kg(bocf_ctx* ctx, int mode, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim,
+                const double* prob, int L, const double* Zf, int Sf, double* acq_out, double* dacq_out);
+
 /* ---- multi-GPU: candidate shards, ONE collective.  One process per GPU, one context per process.  The
  * reference's own candidate parallelism is a pathos process pool over single candidates (uEI_noiseless.py:85-97); here rank
  * r scores the contiguous slice [lo_r, hi_r) of the batch against its resident fit and the ranks exchange only their k
