@@ -1,6 +1,6 @@
 """bocf_amd: MI355X-native GP-posterior + composite-acquisition hot path of BOCF behind the
 reference's multi_outputGP / AcquisitionBase plug-in surface.  See DESIGN.md."""
-from . import _ffi, kern  # noqa: F401
+from . import _ffi, kern, utility_program  # noqa: F401
 from .acquisition_optimizer import AcquisitionOptimizer, Design_space  # noqa: F401
 from .acquisitions import EI, PI, AcquisitionBase, maEI, maPI, uEI_noiseless, uKG, uPI  # noqa: F401
 from .cbo import CBO, CompositeThompsonBatch, Sequential  # noqa: F401
@@ -8,5 +8,6 @@ from .multi_outputGP import multi_outputGP  # noqa: F401
 from .objective import MultiObjective  # noqa: F401
 from .recommend import current_marginal_argmaxes  # noqa: F401
 from .utility import ExpectationUtility, ParameterDistribution, Utility  # noqa: F401
+from .utility_program import TraceError  # noqa: F401
 
 __version__ = "0.1.0"

@@ -19,6 +19,7 @@ KERN_RBF, KERN_SE, KERN_MATERN52, KERN_MATERN32 = 0, 1, 2, 3
 ADD_NOISE, CLIP = 1, 2
 ACQ_EI, ACQ_PI = 0, 1
 UTIL_LINEAR, UTIL_NEG_SQ_DIST, UTIL_NEG_SUM_EXP, UTIL_NEG_EXP_COS, UTIL_ROSENBROCK = 0, 1, 2, 3, 4
+UTIL_PROGRAM = 5        # the utility program staged on the context (bocf_set_utility_program)
 EU_MEAN, EU_CLOSED, EU_MC = 0, 1, 2
 
 _c_double_p = ctypes.POINTER(ctypes.c_double)
@@ -76,6 +77,8 @@ SIGNATURES = {
     "bocf_set_mc_samples": (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int]),
     "bocf_acq_mc": (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int,
                                    _c_double_p, ctypes.c_int, _c_double_p]),
+    "bocf_check_utility_program": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, ctypes.c_int]),
+    "bocf_set_utility_program": (ctypes.c_int, [_ctx_p, ctypes.c_char_p, ctypes.c_long]),
     "bocf_select_topk": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_ll_p, _c_double_p]),
     "bocf_set_eu_samples": (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int, ctypes.c_int]),
     "bocf_expected_utility": (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int,

@@ -184,7 +184,8 @@ class _MonteCarlo(AcquisitionBase):
         thetas = self._thetas()
         if kind in (_ffi.UTIL_NEG_SUM_EXP, _ffi.UTIL_NEG_EXP_COS):
             thetas = np.zeros((thetas.shape[0], 1))        # parameter unused by these utilities
-        acqX = model.acq_mc(X, self._kind, kind, self.utility.device_params, thetas, prob, W=self.W_samples, n_hyps=self.n_hyps_samples)
+        acqX = model.acq_mc(X, self._kind, kind, self.utility.device_params, thetas, prob, W=self.W_samples, n_hyps=self.n_hyps_samples,
+                            program=self.utility.program_blob if kind == _ffi.UTIL_PROGRAM else None)
         return np.reshape(acqX, (X.shape[0], 1))
 
     def _compute_acq_withGradients(self, X):
@@ -204,7 +205,8 @@ class _MonteCarlo(AcquisitionBase):
         if kind in (_ffi.UTIL_NEG_SUM_EXP, _ffi.UTIL_NEG_EXP_COS):
             thetas = np.zeros((thetas.shape[0], 1))
         acqX, dacq_dX = self._device_model().acq_mc_grad(X, kind, self.utility.device_params, thetas, prob, W=self.W_samples,
-                                                         n_hyps=self.n_hyps_samples)
+                                                         n_hyps=self.n_hyps_samples,
+                                                         program=self.utility.program_blob if kind == _ffi.UTIL_PROGRAM else None)
         return np.reshape(acqX, (X.shape[0], 1)), np.reshape(dacq_dX, X.shape)
 
     # ---- utilities outside the device's closed set (utility.py:37-41 accepts ANY callable): the posterior still comes from
@@ -217,7 +219,8 @@ class _MonteCarlo(AcquisitionBase):
             if not getattr(self, "_warned_host_utility", False):
                 warnings.warn("bocf_amd: the utility is a Python callable outside the device's closed set (%s): the posterior "
                               "(mean, variance, gradients) is computed on the GPU, the Monte-Carlo loop over U runs on the HOST -- "
-                              "orders of magnitude slower than a device utility (Utility(..., device=...))"
+                              "orders of magnitude slower than a device utility (Utility(..., device=...); device='program' traces this "
+                              "callable and runs it on the GPU)"
                               % ", ".join(sorted(["linear", "neg_sq_dist", "neg_sum_exp", "neg_exp_cos", "rosenbrock"])), RuntimeWarning,
                               stacklevel=3)
                 self._warned_host_utility = True
@@ -389,6 +392,9 @@ class uKG(AcquisitionBase):
         except NotImplementedError:
             raise NotImplementedError("uKG needs a utility with a device kind (Utility(..., device=...): linear, neg_sq_dist, neg_sum_exp, "
                                       "neg_exp_cos, rosenbrock): the look-ahead runs on the device, there is no host loop for a Python callable")
+        if kind == _ffi.UTIL_PROGRAM:
+            raise NotImplementedError("uKG does not take a utility program (Utility(..., device='program')): the knowledge gradient runs the "
+                                      "compiled-in utilities only (linear, neg_sq_dist, neg_sum_exp, neg_exp_cos, rosenbrock)")
         name = _KIND_NAMES[kind]
         if kind == _ffi.UTIL_LINEAR:
             return _ffi.EU_MEAN, kind

@@ -31,8 +31,12 @@ __global__ __launch_bounds__(256) void best_so_far_kernel(const double* __restri
 }
 
 void launch_best_so_far(const double* mu_train, int N, int m, int linear, int util_kind, const double* theta, int theta_dim, int L,
-                        const double* util_params, double* best, hipStream_t s) {
+                        const double* util_params, double* best, hipStream_t s, const UtilProg* prog) {
   (void)linear;
+  if (util_kind == BOCF_UTIL_PROGRAM) {                    // the interpreter kernel (util_prog.hip): utility_eval stays the closed set
+    launch_best_so_far_prog(mu_train, N, theta, theta_dim, L, best, *prog, s);
+    return;
+  }
   BOCF_LAUNCH(best_so_far_kernel, dim3((unsigned)L), dim3(256), 0, s, mu_train, N, m, util_kind, theta, theta_dim, util_params, best);
 }
 
@@ -149,6 +153,10 @@ __global__ __launch_bounds__(256) void acq_mc_m_kernel(AcqArgs a) {
 
 void launch_acq_mc(const AcqArgs& a, hipStream_t s) {
   if (a.C == 0) return;
+  if (a.util_kind == BOCF_UTIL_PROGRAM) {
+    launch_acq_mc_prog(a, s);
+    return;
+  }
   const dim3 grid((unsigned)((a.C + 3) / 4));
   if (a.m >= 1 && a.m <= 8) {
 #define LM(M) case M: BOCF_LAUNCH((acq_mc_m_kernel<M>), grid, dim3(256), 0, s, a); break;
@@ -290,6 +298,10 @@ __global__ __launch_bounds__(256) void acq_mc_grad_kernel(AcqArgs a) {
 
 void launch_acq_mc_grad(const AcqArgs& a, hipStream_t s) {
   if (a.C == 0) return;
+  if (a.util_kind == BOCF_UTIL_PROGRAM) {
+    launch_acq_mc_grad_prog(a, s);
+    return;
+  }
   const dim3 grid((unsigned)((a.C + 3) / 4));
   if (a.m >= 1 && a.m <= 8) {
 #define LM(M) case M: BOCF_LAUNCH((acq_mc_grad_kernel<M>), grid, dim3(256), 0, s, a); break;

@@ -147,6 +147,9 @@ struct bocf_ctx {
   long long best_epoch = -1; int best_sig = -1;   // what c->best was computed from: mu_epoch and (linear, utility kind, group); reset when the parameters are re-uploaded
   int S_mc = 0;
   bool have_acq = false;
+  // ---- the resident utility program (bocf_set_utility_program; util_prog.hip): stays until it is replaced
+  DevBuf prog_buf;
+  UtilProg prog;
   DevBuf blk_idx, blk_val, out_idx, out_val;
   // ---- expected utility of the recommendation step (bocf_set_eu_samples / bocf_expected_utility): buffers of its own, so the
   // acquisition state above (acq, dacq, theta / prob / params, Wt, the best-so-far cache) is left as it was
@@ -193,6 +196,9 @@ struct bocf_ctx {
   DevBuf kg_V, kg_W, kg_cov, kg_s2c, kg_dcov, kg_dmean, kg_dvar, kg_par, kg_v0, kg_astar, kg_AB, kg_out, kg_dout;
 };
 
+// util_prog.hip: what every entry point checks before it evaluates the resident program (utility kind BOCF_UTIL_PROGRAM): one is resident,
+// no util_params, and it was built for these m outputs per hyper-sample and this theta_dim.  Errors name `who`.
+int bocf_check_resident_program(bocf_ctx* c, const char* who, int m, int theta_dim, int n_util_params);
 // the resident Thompson samples belong to one posterior and one candidate set: dropped by every fit, data change and candidate upload
 void bocf_thompson_drop(bocf_ctx* c);
 // the resident reference set belongs to one posterior: dropped by every fit and data change (NOT by a candidate upload)

@@ -297,6 +297,23 @@ void launch_grad_kernel(const double* Xs, long strideXs, int N, int Np, int d, i
                         int m, hipStream_t s, const int* kids = nullptr);
 
 // ---------------------------------------------------------------------------------------
+// utility programs (util_prog.hip; layout and limits: include/bocf_hip.h)
+// ---------------------------------------------------------------------------------------
+// The program resident on a context as the HOST sees it: the numbers of its validated header and the device copy of the blob.  The
+// launchers below take it when the utility kind is BOCF_UTIL_PROGRAM and dispatch to the interpreter kernels.
+struct UtilProg {
+  const unsigned* dev = nullptr;     // device copy of the whole blob (nullptr: no program resident)
+  int m = 0, theta_dim = 0, n_slots = 0, n_val = 0, n_grad = 0, n_const = 0;
+  int val_out = 0;
+  int grad_out[1 + BOCF_MAX_M] = {0};
+};
+// 0 when the blob is a valid program for m outputs and theta_dim parameters (m, theta_dim < 0: whatever its header states), else -1 with
+// the offending field in bocf_last_error(); *out (optional) receives the header numbers (dev stays nullptr)
+int util_prog_check(const char* who, const void* blob, long nbytes, int m, int theta_dim, UtilProg* out);
+// threads per workgroup (64, 128 or 256) and bytes of dynamic LDS of a program launch: (m + slots) x threads x 8 bytes
+void util_prog_geometry(const UtilProg& p, int* threads, size_t* lds_bytes);
+
+// ---------------------------------------------------------------------------------------
 // acquisition + selection kernels (acq.hip)
 // ---------------------------------------------------------------------------------------
 struct AcqArgs {
@@ -315,9 +332,10 @@ struct AcqArgs {
   double* dacq;            // device (C, d)
   int accumulate;          // 0: acq/dacq are written; 1: added to (hyper-sample h > 0 of the h-loop, maEI.py:85-97)
   double scale;            // 1 / H
+  const UtilProg* prog;    // HOST pointer, read by the launchers only: the resident program when util_kind is BOCF_UTIL_PROGRAM
 };
 void launch_best_so_far(const double* mu_train, int N, int m, int linear, int util_kind, const double* theta, int theta_dim, int L,
-                        const double* util_params, double* best, hipStream_t s);
+                        const double* util_params, double* best, hipStream_t s, const UtilProg* prog = nullptr);
 void launch_acq_linear(const AcqArgs& a, hipStream_t s);
 void launch_acq_mc(const AcqArgs& a, hipStream_t s);
 void launch_acq_linear_grad(const AcqArgs& a, hipStream_t s);
@@ -340,8 +358,15 @@ struct EuArgs {
   double* grad;            // device (C, d) or nullptr (value only)
   int accumulate;          // 0: val/grad are written; 1: added to (hyper-sample h > 0)
   double scale;            // n_hyps with one resident hyper-sample, else 1
+  const UtilProg* prog;    // HOST pointer, read by the launcher only: the resident program when util_kind is BOCF_UTIL_PROGRAM
 };
 void launch_eu(const EuArgs& a, hipStream_t s);
+// the interpreter kernels behind the launchers above and launch_thompson_util (util_prog.hip): same geometry, same reduction order
+void launch_best_so_far_prog(const double* mu_train, int N, const double* theta, int theta_dim, int L, double* best, const UtilProg& p, hipStream_t s);
+void launch_acq_mc_prog(const AcqArgs& a, hipStream_t s);
+void launch_acq_mc_grad_prog(const AcqArgs& a, hipStream_t s);
+void launch_eu_prog(const EuArgs& a, hipStream_t s);
+void launch_thompson_util_prog(const double* F, int C, int S, const double* theta, int theta_dim, double* u, long ldu, const UtilProg& p, hipStream_t s);
 // two-stage top-k (value desc, index asc); out: idx (k) int64, val (k)
 void launch_topk(const double* acq, int C, int k, long long* blk_idx, double* blk_val, long long* out_idx, double* out_val, hipStream_t s);
 int topk_num_blocks(int C);
@@ -364,7 +389,7 @@ void launch_post_sample(const double* U, long ldu, long strideU, const double* Z
                         hipStream_t s);
 // u[s][c] = U(theta_s, F[:, c, s]) (utility_dev.h) for one sample block F (m, C, S)
 void launch_thompson_util(const double* F, int m, int C, int S, int util_kind, const double* theta, int theta_dim, const double* params, double* u,
-                          long ldu, hipStream_t s);
+                          long ldu, hipStream_t s, const UtilProg* prog = nullptr);
 
 // ---------------------------------------------------------------------------------------
 // look-ahead posterior and discrete composite knowledge gradient (kg.hip)

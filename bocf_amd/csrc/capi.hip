@@ -110,7 +110,7 @@ extern "C" void bocf_destroy(bocf_ctx* c) {
                     &c->gval, &c->shard_meta, &c->chol_flags, &c->eu_theta, &c->eu_rows, &c->eu_Z, &c->eu_val, &c->eu_grad,
                     &c->ts_X, &c->ts_K, &c->ts_V, &c->ts_mp, &c->ts_mu, &c->ts_Z, &c->ts_jit, &c->ts_u, &c->ts_theta, &c->ts_params, &c->ts_out,
                     &c->kg_XA, &c->kg_VA, &c->kg_Wa, &c->kg_muA, &c->kg_s2A, &c->kg_nug, &c->kg_V, &c->kg_W, &c->kg_cov, &c->kg_s2c, &c->kg_dcov, &c->kg_dmean, &c->kg_dvar,
-                    &c->kg_par, &c->kg_v0, &c->kg_astar, &c->kg_AB, &c->kg_out, &c->kg_dout};
+                    &c->kg_par, &c->kg_v0, &c->kg_astar, &c->kg_AB, &c->kg_out, &c->kg_dout, &c->prog_buf};
   for (DevBuf* b : bufs) b->release();
   if (c->infer_out) (void)hipHostFree(c->infer_out);
   if (c->tile_ctr) (void)hipFree(c->tile_ctr);
@@ -651,7 +651,7 @@ static void acq_over_hyper_samples(bocf_ctx* c, AcqArgs a, int m, int linear, Ac
       c->best_sig = sig;
       if (!cached)
       launch_best_so_far(c->mu_train.as<double>() + (size_t)gb * m * c->N, c->N, m, linear, a.util_kind, a.theta, a.theta_dim, a.L,
-                         a.util_params, c->best.as<double>(), c->stream);
+                         a.util_params, c->best.as<double>(), c->stream, a.prog);
     }
     a.mean = mean + (size_t)h * m * a.ld;
     a.var = var + (size_t)h * m * a.ld;
@@ -678,6 +678,7 @@ static int run_acq(bocf_ctx* c, int m, bool linear, bool grad, AcqLaunch launch,
   a.m = m; a.C = c->C; a.L = L; a.kind = kind; a.util_kind = util_kind; a.theta_dim = theta_dim > 0 ? theta_dim : 1;
   a.theta = c->theta.as<double>(); a.prob = c->prob.as<double>(); a.best = c->best.as<double>();
   a.util_params = c->params.as<double>(); a.n_util_params = n_util_params; a.acq = c->acq.as<double>();
+  a.prog = &c->prog;
   if (!linear) { a.Wt = c->Wt.as<double>(); a.S = c->S_mc; }
   if (grad) { a.dmean = c->dmean.as<double>(); a.dvar = c->dvar.as<double>(); a.ldg = c->pred_cap; a.d = c->d; a.dacq = c->dacq.as<double>(); }
   acq_over_hyper_samples(c, a, m, linear ? 1 : 0, launch);
@@ -720,10 +721,11 @@ extern "C" int bocf_set_mc_samples(bocf_ctx* c, const double* W, int S) {
 
 // the utility checks of bocf_acq_mc and bocf_acq_mc_grad, in their order (errors name `me`): outputs per hyper-sample, or -1
 static int mc_group_size(bocf_ctx* c, const char* me, int util_kind, const double* util_params, int n_util_params, int theta_dim) {
-  if (util_kind < 0 || util_kind > BOCF_UTIL_ROSENBROCK) return fail(me, "unknown utility kind");
+  if (util_kind < 0 || util_kind > BOCF_UTIL_PROGRAM) return fail(me, "unknown utility kind");
   if (c->S_mc < 1) return fail(me, "no Monte-Carlo samples set (bocf_set_mc_samples)");
   const int m = group_size(c, me);
   if (m < 0) return -1;
+  if (util_kind == BOCF_UTIL_PROGRAM) return bocf_check_resident_program(c, me, m, theta_dim, n_util_params) ? -1 : m;
   if ((util_kind == BOCF_UTIL_LINEAR || util_kind == BOCF_UTIL_NEG_SQ_DIST) && theta_dim != m) return fail(me, "theta_dim must equal m");
   if (util_kind == BOCF_UTIL_ROSENBROCK && (theta_dim < 1 || (m & 1))) return fail(me, "rosenbrock utility needs theta_dim >= 1 and even m");
   if (util_kind == BOCF_UTIL_NEG_EXP_COS && n_util_params != m) return fail(me, "neg_exp_cos needs m weights");
@@ -773,10 +775,13 @@ extern "C" int bocf_expected_utility(bocf_ctx* c, int mode, int util_kind, const
   if (!c || !c->fitted) return fail(me, "model not fitted");
   if (c->canned) return fail(me, "the context holds a host-given posterior (bocf_set_posterior): fit first");
   if (mode < BOCF_EU_MEAN || mode > BOCF_EU_MC) return fail(me, "unknown mode");
-  if (util_kind < 0 || util_kind > BOCF_UTIL_ROSENBROCK) return fail(me, "unknown utility kind");
+  if (util_kind < 0 || util_kind > BOCF_UTIL_PROGRAM) return fail(me, "unknown utility kind");
   const int m = group_size(c, me);
   if (m < 0) return -1;
   if (L < 1 || theta_dim < 1 || !theta) return fail(me, "theta must be (L >= 1, theta_dim >= 1)");
+  if (mode == BOCF_EU_CLOSED && util_kind == BOCF_UTIL_PROGRAM)
+    return fail(me, "a utility program has no closed-form expectation (BOCF_EU_CLOSED): use the Monte-Carlo mode");
+  if (mode == BOCF_EU_MC && util_kind == BOCF_UTIL_PROGRAM && bocf_check_resident_program(c, me, m, theta_dim, n_util_params)) return -1;
   if ((mode == BOCF_EU_MEAN || util_kind == BOCF_UTIL_LINEAR || util_kind == BOCF_UTIL_NEG_SQ_DIST) && theta_dim != m)
     return fail(me, "theta_dim must equal m");
   if (mode != BOCF_EU_MEAN && util_kind == BOCF_UTIL_ROSENBROCK && (m & 1)) return fail(me, "rosenbrock utility needs even m");
@@ -832,6 +837,7 @@ extern "C" int bocf_expected_utility(bocf_ctx* c, int mode, int util_kind, const
   a.rows = c->eu_rows.as<int>(); a.Zt = c->eu_Z.as<double>(); a.S = c->eu_S;
   a.val = c->eu_val.as<double>(); a.grad = need_grad ? c->eu_grad.as<double>() : nullptr;
   a.scale = H == 1 ? (double)n_hyps : 1.0;
+  a.prog = &c->prog;
   for (int h = 0; h < nh; ++h) {
     a.mean = c->mean.as<double>() + (size_t)h * m * a.ld;
     a.var = c->var.as<double>() + (size_t)h * m * a.ld;

@@ -185,6 +185,7 @@ extern "C" int bocf_acq_kg(bocf_ctx* c, int mode, int util_kind, const double* u
   static const char* who = "bocf_acq_kg";
   if (bocf_check_posterior(c, who)) return -1;
   if (mode < BOCF_EU_MEAN || mode > BOCF_EU_MC) return fail(who, "unknown mode");
+  if (util_kind == BOCF_UTIL_PROGRAM) return fail(who, "the knowledge gradient does not take a utility program (BOCF_UTIL_PROGRAM): use one of the compiled-in utilities");
   if (util_kind < BOCF_UTIL_LINEAR || util_kind > BOCF_UTIL_ROSENBROCK) return fail(who, "unknown utility kind");
   int j0, mg, m;
   if (bocf_group_range(c, who, -1, &j0, &mg, &m)) return -1;

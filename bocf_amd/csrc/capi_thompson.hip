@@ -236,9 +236,10 @@ extern "C" int bocf_thompson_select(bocf_ctx* c, int util_kind, const double* ut
   const int C = c->C, H = (int)c->ts_S.size(), per = c->m / H;
   if (k < 1 || k > 64 || k > C) return fail(who, "k out of range (1 .. min(C, 64))");
   if (!idx_out || (theta_dim > 0 && !theta) || theta_dim < 0) return fail(who, "null argument / bad theta_dim");
-  if (util_kind < BOCF_UTIL_LINEAR || util_kind > BOCF_UTIL_ROSENBROCK) return fail(who, "unknown utility kind");
+  if (util_kind < BOCF_UTIL_LINEAR || util_kind > BOCF_UTIL_PROGRAM) return fail(who, "unknown utility kind");
   if (n_util_params < 0 || n_util_params > BOCF_MAX_M || (n_util_params > 0 && !util_params)) return fail(who, "too many utility parameters / null");
   if (per > BOCF_MAX_M) return fail(who, "more outputs per hyper-sample than the device utilities take (16)");
+  if (util_kind == BOCF_UTIL_PROGRAM && bocf_check_resident_program(c, who, per, theta_dim, n_util_params)) return -1;
   HIPCHK(hipSetDevice(c->device));
   // theta rows widened to at least m' columns (the utilities read theta[j] for j < m'), parameters to BOCF_MAX_M: zeros behind
   const int tw = theta_dim > per ? theta_dim : (per > 1 ? per : 1);
@@ -262,7 +263,7 @@ extern "C" int bocf_thompson_select(bocf_ctx* c, int util_kind, const double* ut
     for (int h = 0; h < H; ++h) {
       if (c->ts_S[h] == 0) continue;
       launch_thompson_util(c->ts_F[h].as<double>(), per, C, c->ts_S[h], util_kind, c->ts_theta.as<double>() + (size_t)p0 * tw, tw, c->ts_params.as<double>(),
-                           c->ts_u.as<double>() + (size_t)p0 * C, C, c->stream);
+                           c->ts_u.as<double>() + (size_t)p0 * C, C, c->stream, &c->prog);
       p0 += c->ts_S[h];
     }
     for (int p = 0; p < P; ++p)

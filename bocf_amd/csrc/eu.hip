@@ -91,6 +91,10 @@ __global__ __launch_bounds__(256) void eu_kernel(EuArgs a) {
 
 void launch_eu(const EuArgs& a, hipStream_t s) {
   if (a.C == 0) return;
+  if (a.util_kind == BOCF_UTIL_PROGRAM && a.mode == BOCF_EU_MC) {   // (the mean form ignores the kind; the entry point rejects the closed form)
+    launch_eu_prog(a, s);
+    return;
+  }
   const dim3 grid((unsigned)((a.C + 3) / 4));
   if (a.m >= 1 && a.m <= 8) {
 #define LM(M) case M: BOCF_LAUNCH((eu_kernel<M>), grid, dim3(256), 0, s, a); break;

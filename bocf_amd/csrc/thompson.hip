@@ -288,8 +288,12 @@ __global__ __launch_bounds__(256) void thompson_util_kernel(const double* __rest
 }
 
 void launch_thompson_util(const double* F, int m, int C, int S, int util_kind, const double* theta, int theta_dim, const double* params, double* u,
-                          long ldu, hipStream_t s) {
+                          long ldu, hipStream_t s, const UtilProg* prog) {
   if (C <= 0 || S <= 0) return;
+  if (util_kind == BOCF_UTIL_PROGRAM) {
+    launch_thompson_util_prog(F, C, S, theta, theta_dim, u, ldu, *prog, s);
+    return;
+  }
   BOCF_LAUNCH(thompson_util_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)S), dim3(256), 0, s, F, m, C, S, util_kind, theta, theta_dim, params,
               u, ldu);
 }

@@ -119,6 +119,7 @@ class multi_outputGP(object):
         self._n_resident = None       # candidates resident on the device (unknown after a fit)
         self._fit_key = None
         self._W_key = None
+        self._prog_key = None
         self._Z_key = None
         self._ref_key = None          # reference set resident on the device (set_reference_points)
         self._cov_points = self._next_point = self._grad_point = None
@@ -156,6 +157,7 @@ class multi_outputGP(object):
         st["_cand_token"] = None
         st["_n_resident"] = None
         st["_W_key"] = None
+        st["_prog_key"] = None
         st["_Z_key"] = None
         st["_ref_key"] = None
         st["_query_cache"] = st["_grad_cache"] = None
@@ -264,6 +266,7 @@ class multi_outputGP(object):
         _ffi.check(rc, "bocf_fit")
         self._fitted = False
         self._W_key = None
+        self._prog_key = None
         self._Z_key = None
         self._cand_token = None
         self._n_resident = None       # candidates resident on the device (unknown after a fit)
@@ -355,6 +358,7 @@ class multi_outputGP(object):
         _ffi.check(rc, "bocf_infer")
         self._fitted = False
         self._W_key = None
+        self._prog_key = None
         self._Z_key = None
         self._cand_token = None
         self._n_resident = None       # candidates resident on the device (unknown after a fit)
@@ -444,6 +448,7 @@ class multi_outputGP(object):
             _ffi.check(rc, "bocf_hmc_streamed")
         self._fitted = False
         self._W_key = None
+        self._prog_key = None
         self._Z_key = None
         self._cand_token = None
         self._n_resident = None       # candidates resident on the device (unknown after a fit)
@@ -785,6 +790,8 @@ class multi_outputGP(object):
         dev = path_groups if self._H > 1 else np.zeros(P, dtype=int)
         kind = utility.device_kind(self.output_dim)
         params = utility.device_params
+        if kind == _ffi.UTIL_PROGRAM:
+            self.set_utility_program(utility.program_blob)
         self._set_candidates(X)
         order = []
         for g in sorted(set(dev.tolist())):
@@ -906,9 +913,23 @@ class multi_outputGP(object):
                                                         _ffi.dptr(acq), _ffi.dptr(dacq)), "bocf_acq_linear_grad")
         return acq, dacq
 
-    def acq_mc_grad(self, X, util_kind, util_params, thetas, prob, W=None, n_hyps=None):
-        """(acq (n,), d acq/dX (n, d)) of the Monte-Carlo EI (bocf_acq_mc_grad)."""
+    def set_utility_program(self, blob):
+        """Stage a utility program (the blob of utility_program.Program.to_bytes(), Utility.program_blob) on the device for the calls
+        with utility kind _ffi.UTIL_PROGRAM; it stays resident until another one is set.  Key-cached like set_mc_samples: an L-BFGS
+        run sends the same program hundreds of times."""
+        if blob is None:
+            raise ValueError("utility kind 'program' needs the program blob (Utility(..., device='program').program_blob)")
+        blob = bytes(blob)
+        if blob == self._prog_key:
+            return
+        _ffi.check(_ffi.load().bocf_set_utility_program(self._context().handle, blob, len(blob)), "bocf_set_utility_program")
+        self._prog_key = blob
+
+    def acq_mc_grad(self, X, util_kind, util_params, thetas, prob, W=None, n_hyps=None, program=None):
+        """(acq (n,), d acq/dX (n, d)) of the Monte-Carlo EI (bocf_acq_mc_grad); `program`: the blob for utility kind UTIL_PROGRAM."""
         self._begin_acq(n_hyps, False)
+        if util_kind == _ffi.UTIL_PROGRAM:
+            self.set_utility_program(program)
         if W is not None:
             self.set_mc_samples(W)
         n = self._set_candidates(np.atleast_2d(X))
@@ -933,9 +954,11 @@ class multi_outputGP(object):
         _ffi.check(_ffi.load().bocf_set_mc_samples(self._context().handle, _ffi.dptr(W), W.shape[0]), "bocf_set_mc_samples")
         self._W_key = key
 
-    def acq_mc(self, X, kind, util_kind, util_params, thetas, prob, W=None, fetch=True, n_hyps=None):
-        """Monte-Carlo EI/PI of a device utility over the batch X (bocf_acq_mc)."""
+    def acq_mc(self, X, kind, util_kind, util_params, thetas, prob, W=None, fetch=True, n_hyps=None, program=None):
+        """Monte-Carlo EI/PI of a device utility over the batch X (bocf_acq_mc); `program`: the blob for utility kind UTIL_PROGRAM."""
         self._begin_acq(n_hyps, False)
+        if util_kind == _ffi.UTIL_PROGRAM:
+            self.set_utility_program(program)
         if W is not None:
             self.set_mc_samples(W)
         n = self._set_candidates(np.atleast_2d(X)) if X is not None else None
@@ -993,6 +1016,8 @@ class multi_outputGP(object):
             kind = 0 if mode == _ffi.EU_MEAN else utility.device_kind(self.output_dim)
             if util_params is None:
                 util_params = utility.device_params
+            if kind == _ffi.UTIL_PROGRAM and mode == _ffi.EU_MC:
+                self.set_utility_program(utility.program_blob)
         elif isinstance(utility, str):
             from .utility import _DEVICE_KINDS
             kind = _DEVICE_KINDS[utility]

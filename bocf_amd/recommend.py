@@ -31,7 +31,7 @@ from .acquisition_optimizer import _bounds_of, lbfgsb_batched, samples_multidime
 N_Z_SAMPLES = 50                  # cbo.py:200
 _CLOSED_KINDS = ("neg_sq_dist", "neg_sum_exp", "rosenbrock")
 _KIND_NAMES = {_ffi.UTIL_LINEAR: "linear", _ffi.UTIL_NEG_SQ_DIST: "neg_sq_dist", _ffi.UTIL_NEG_SUM_EXP: "neg_sum_exp",
-               _ffi.UTIL_NEG_EXP_COS: "neg_exp_cos", _ffi.UTIL_ROSENBROCK: "rosenbrock"}
+               _ffi.UTIL_NEG_EXP_COS: "neg_exp_cos", _ffi.UTIL_ROSENBROCK: "rosenbrock", _ffi.UTIL_PROGRAM: "program"}
 
 
 def branch_of(utility, expectation_utility=None):
@@ -113,8 +113,9 @@ def device_evaluator(model, branch, utility, parameters, Z=None, n_hyps=None, ki
         kind = _KIND_NAMES[utility.device_kind(model.output_dim)]
 
     def ev(X, rows, grad=False):
-        out = model.expected_utility(X, branch, kind if branch != "mean" else None, thetas, rows, Z=Z, n_hyps=n_hyps, grad=grad,
-                                     util_params=utility.device_params)
+        # (a utility program travels with its Utility: the model stages the blob)
+        out = model.expected_utility(X, branch, (utility if kind == "program" else kind) if branch != "mean" else None, thetas, rows, Z=Z,
+                                     n_hyps=n_hyps, grad=grad, util_params=utility.device_params)
         return out if grad else (out, None)
     return ev
 

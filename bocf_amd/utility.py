@@ -1,10 +1,14 @@
 """Utility / ParameterDistribution / ExpectationUtility with the reference's signatures
 (utility.py:6-48, parameter_distribution.py:5-29, expectation_utility.py:3-9), plus the
 DEVICE specification of the utility: the Monte-Carlo acquisitions evaluate U on the GPU, so U
-must be one of the closed set of utilities the reference's experiment scripts use."""
+is one of the closed set of utilities the reference's experiment scripts use, or -- on request,
+device="program" -- the user's own callable traced into a utility program (utility_program.py)."""
+import pickle
+
 import numpy as np
 
 from . import _ffi
+from . import utility_program as _up
 
 
 class ParameterDistribution(object):
@@ -41,7 +45,7 @@ class ExpectationUtility(object):
 
 
 _DEVICE_KINDS = {"linear": _ffi.UTIL_LINEAR, "neg_sq_dist": _ffi.UTIL_NEG_SQ_DIST, "neg_sum_exp": _ffi.UTIL_NEG_SUM_EXP,
-                 "neg_exp_cos": _ffi.UTIL_NEG_EXP_COS, "rosenbrock": _ffi.UTIL_ROSENBROCK}
+                 "neg_exp_cos": _ffi.UTIL_NEG_EXP_COS, "rosenbrock": _ffi.UTIL_ROSENBROCK, "program": _ffi.UTIL_PROGRAM}
 
 
 def _host_func(kind, params):
@@ -70,6 +74,12 @@ class Utility(object):
     utility.py:6-48 plus `device`: name of the device utility ("linear", "neg_sq_dist",
     "neg_sum_exp", "neg_exp_cos", "rosenbrock") and `device_params` (weights c of neg_exp_cos).
     `func` may be omitted for a device utility.
+
+    device="program" asks for the user's own `func` on the device: it is traced (utility_program.trace) at the first
+    device_kind(m), where the number of outputs is known, into a straight-line program that the device interprets; the blob is
+    kept in `program_blob`.  A callable that cannot be traced (data-dependent control flow) or a program beyond the limits of
+    include/bocf_hip.h raises -- an explicit request never falls back to the host.  Without a `dfunc` the program's own gradient
+    section serves as the host dfunc.  Never chosen implicitly: device=None only recognises the closed set.
     """
 
     def __init__(self, func=None, dfunc=None, parameter_dist=None, linear=False, device=None, device_params=None):
@@ -77,10 +87,14 @@ class Utility(object):
             device = "linear"
         if device is not None and device not in _DEVICE_KINDS:
             raise ValueError("unknown device utility %r (have: %s)" % (device, ", ".join(sorted(_DEVICE_KINDS))))
+        if device == "program" and func is None:
+            raise ValueError("device='program' traces `func`: give the callable")
         self.device = device
         self.device_params = None if device_params is None else np.asarray(device_params, dtype=float)
         self.func = func if func is not None else (_host_func(device, device_params) if device else None)
-        self.dfunc = dfunc
+        self.dfunc = dfunc if (dfunc is not None or device != "program") else self._program_dfunc
+        self.program_blob = None
+        self._program = None
         self.parameter_dist = parameter_dist
         self.linear = linear
 
@@ -89,6 +103,9 @@ class Utility(object):
         no `device` argument) the callable is RECOGNISED: it is probed at a handful of fixed points (private RNG, the global
         np.random stream is not touched) and compared with the closed set of device utilities; `m` is the number of model
         outputs (needed when the utility parameter does not determine it).  No match -> NotImplementedError."""
+        if self.device == "program":
+            self._ensure_program(m)
+            return _ffi.UTIL_PROGRAM
         if self.device is None and self.func is not None:
             self._recognise(m)
         if self.device is None:
@@ -96,6 +113,63 @@ class Utility(object):
                 "this Utility wraps a Python callable that is none of the device utilities; the Monte-Carlo acquisitions run on "
                 "the GPU and need one of %s (Utility(..., device=...))" % ", ".join(sorted(_DEVICE_KINDS)))
         return _DEVICE_KINDS[self.device]
+
+    # ---- device="program"
+    def _theta_dim(self):
+        dist = self.parameter_dist
+        support = getattr(dist, "support", None)
+        if support is not None and len(support) > 0:
+            return int(np.asarray(support[0]).size)
+        if dist is not None and getattr(dist, "sample_generator", None) is not None:
+            state = np.random.get_state()                  # the probe draw must not move the global stream
+            try:
+                return int(np.asarray(dist.sample(1)[0]).size)
+            finally:
+                np.random.set_state(state)
+        return 1
+
+    def _ensure_program(self, m=None):
+        """The traced program of `func` for m outputs (traced once; another m traces again)."""
+        if self._program is not None and (m is None or int(m) == self._program.m):
+            return self._program
+        if m is None:
+            m = self._theta_dim()
+        self._program = _up.trace(self.func, int(m), self._theta_dim())
+        self.program_blob = self._program.to_bytes()
+        return self._program
+
+    def _program_dfunc(self, parameter, y):
+        return self._ensure_program(np.asarray(y).shape[0]).grad(np.atleast_1d(parameter), y)
+
+    def _program_func(self, parameter, y):
+        return self._ensure_program(np.asarray(y).shape[0]).value(np.atleast_1d(parameter), y)
+
+    def __getstate__(self):
+        st = dict(self.__dict__)
+        if self.device == "program":
+            st["_program"] = None
+            if st["dfunc"] == self._program_dfunc:
+                st["dfunc"] = None
+            if st["func"] == self._program_func:
+                st["func"] = None
+            else:
+                try:
+                    pickle.dumps(st["func"])
+                except Exception:
+                    if self.program_blob is None:
+                        raise
+                    st["func"] = None                      # (a lambda: the traced program stands in for it after unpickling)
+        return st
+
+    def __setstate__(self, st):
+        self.__dict__.update(st)
+        if self.device == "program":
+            if self.program_blob is not None:
+                self._program = _up.Program.from_bytes(self.program_blob)
+            if self.func is None:
+                self.func = self._program_func
+            if self.dfunc is None:
+                self.dfunc = self._program_dfunc
 
     def _recognise(self, m):
         support = getattr(self.parameter_dist, "support", None)

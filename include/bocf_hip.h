@@ -38,14 +38,45 @@ enum { BOCF_ACQ_EI = 0,      /* maEI.py:96 / uEI_noiseless.py:80 */
        BOCF_ACQ_PI = 1 };    /* maPI.py:91-92 / uPI.py:83 (jitter 1e-6) */
 
 /* device utility functions U(theta, y), y in R^m -- the closed set the reference's experiment
- * scripts use (arbitrary Python callables cannot run on the device):
+ * scripts use, compiled in (any other straight-line callable runs as a utility PROGRAM, below):
  *   LINEAR       theta . y                              test_1b.py:89-90     theta_dim = m
  *   NEG_SQ_DIST  -sum_j (y_j - theta_j)^2               test_1a.py:89-92     theta_dim = m
  *   NEG_SUM_EXP  -sum_j exp(y_j)                        test_2a.py:60-62     theta unused
  *   NEG_EXP_COS  -sum_j c_j e^{-y_j/pi} cos(pi y_j)     test_3a.py:52-57     util_params = c (m)
  *   ROSENBROCK   -sum_{j<m/2} (a-y_j)^2 + 100 y_{j+m/2}^2   test_5a.py:48-52  a = theta[0] */
 enum { BOCF_UTIL_LINEAR = 0, BOCF_UTIL_NEG_SQ_DIST = 1, BOCF_UTIL_NEG_SUM_EXP = 2,
-       BOCF_UTIL_NEG_EXP_COS = 3, BOCF_UTIL_ROSENBROCK = 4 };
+       BOCF_UTIL_NEG_EXP_COS = 3, BOCF_UTIL_ROSENBROCK = 4,
+       BOCF_UTIL_PROGRAM = 5 };  /* the utility program resident on the context, see below */
+
+/* ---- utility programs: a user's own U(theta, y) on the device without recompiling.  The host traces the user's callable into a
+ * STRAIGHT-LINE program (bocf_amd/utility_program.py: no branches, no loops; dU/dy is derived at trace time and is ordinary program
+ * output), the device interprets it inside the Monte-Carlo kernels (util_prog.hip).  With util_kind = BOCF_UTIL_PROGRAM the Monte-Carlo
+ * acquisitions, the Monte-Carlo expected utility and the Thompson selection evaluate the program staged on the context; n_util_params
+ * must be 0 and theta_dim and the outputs per hyper-sample must be those the program was built for.  The closed-form expected utility and
+ * the knowledge gradient do not take it.  Non-finite utility values are the caller's responsibility: the program computes what its
+ * arithmetic gives (log of a negative number, a division by zero ...), nothing is trapped or replaced.
+ *
+ * The blob (little endian, 8-byte units):
+ *   header  32 x uint32:  [0] magic BOCF_PROG_MAGIC  [1] version BOCF_PROG_VERSION  [2] m  [3] theta_dim  [4] slots  [5] instructions of the
+ *           value section  [6] instructions of the value+gradient section  [7] constants  [8] slot of U after the value section
+ *           [9] slot of U and [10 + j] slot of dU/dy_j (j < m) after the value+gradient section; the remaining words are 0
+ *   value section, then value+gradient section: one instruction = 2 x uint32
+ *           word 0 = opcode | destination slot << 8,   word 1 = operand a | operand b << 16   (a unary operation repeats a as b)
+ *           operand = kind << 14 | index:  kind 0 slot, 1 input y_index, 2 parameter theta_index, 3 constant-pool entry
+ *   constant pool: float64 each
+ * total 128 + 8 (instructions + constants) bytes.  Each section starts with every slot unwritten, runs its instructions in order and leaves
+ * its outputs in the slots the header names.  The arithmetic is IEEE double without contraction, one operation per instruction. */
+#define BOCF_PROG_MAGIC 0x47505542u
+#define BOCF_PROG_VERSION 1
+#define BOCF_PROG_HEADER_WORDS 32
+#define BOCF_PROG_MAX_INSTR 1024   /* instructions per section */
+#define BOCF_PROG_MAX_SLOTS 64     /* per-sample value slots (the device keeps them in LDS) */
+#define BOCF_PROG_MAX_CONSTS 256   /* constant-pool entries */
+enum { BOCF_OP_ADD = 0, BOCF_OP_SUB, BOCF_OP_MUL, BOCF_OP_DIV, BOCF_OP_NEG, BOCF_OP_ABS, BOCF_OP_SIGN, BOCF_OP_SQRT, BOCF_OP_EXP, BOCF_OP_LOG,
+       BOCF_OP_SIN, BOCF_OP_COS, BOCF_OP_TANH, BOCF_OP_POW, BOCF_OP_MIN, BOCF_OP_MAX,
+       BOCF_OP_GE,               /* a >= b ? 1.0 : 0.0 */
+       BOCF_OP_COUNT };
+enum { BOCF_OPERAND_SLOT = 0, BOCF_OPERAND_INPUT = 1, BOCF_OPERAND_PARAM = 2, BOCF_OPERAND_CONST = 3 };
 
 int bocf_version(void);
 const char* bocf_last_error(void);
@@ -301,6 +332,18 @@ int bocf_acq_mc(bocf_ctx* ctx, int kind, int util_kind, const double* util_param
  * device utility (the dfunc of the experiment scripts). */
 int bocf_acq_mc_grad(bocf_ctx* ctx, int util_kind, const double* util_params, int n_util_params, const double* theta,
                      int theta_dim, const double* prob, int L, double* acq_out, double* dacq_out);
+
+/* Utility programs (layout above).  bocf_check_utility_program is host-only and takes no context: it accepts the blob only if its size, magic
+ * and version are right, m and theta_dim are the ones given, both section lengths, the slot count and the constant count are within the
+ * limits, every opcode is known, every destination and every slot operand is below the slot count, a slot is read only after the section
+ * wrote it, every input index is below m, every parameter index below theta_dim, every constant index below the constant count, every
+ * constant is finite and every output slot was written by its section -- so an accepted program cannot address outside its slot file or
+ * its argument arrays and its interpreter loop runs a validated number of steps.  Returns 0, or < 0 with the offending field named in the
+ * error text.  bocf_set_utility_program runs the same check (for the m and theta_dim the header states) and stages the blob on the
+ * context, where it stays until it is replaced (like the samples of bocf_set_mc_samples); it invalidates the best-so-far cache.  A rejected
+ * blob leaves the resident program as it was and never reaches a launch. */
+int bocf_check_utility_program(const void* blob, long nbytes, int m, int theta_dim);
+int bocf_set_utility_program(bocf_ctx* ctx, const void* blob, long nbytes);
 
 /* Selection on the last acquisition vector: indices of the k largest values, ties to the lowest
  * index -- np.argsort(-acq)[:k] of AnchorPointsGenerator.get (anchor_points_generator.py:59-61)
