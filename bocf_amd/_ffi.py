@@ -21,6 +21,13 @@ ACQ_EI, ACQ_PI = 0, 1
 UTIL_LINEAR, UTIL_NEG_SQ_DIST, UTIL_NEG_SUM_EXP, UTIL_NEG_EXP_COS, UTIL_ROSENBROCK = 0, 1, 2, 3, 4
 UTIL_PROGRAM = 5        # the utility program staged on the context (bocf_set_utility_program)
 EU_MEAN, EU_CLOSED, EU_MC = 0, 1, 2
+EU_MODES = {"mean": EU_MEAN, "closed": EU_CLOSED, "mc": EU_MC}
+
+
+def eu_mode(mode):
+    """The EU_* value of an inner-expectation mode given by name or by value."""
+    return EU_MODES[mode] if isinstance(mode, str) else int(mode)
+
 
 _c_double_p = ctypes.POINTER(ctypes.c_double)
 _c_ll_p = ctypes.POINTER(ctypes.c_longlong)

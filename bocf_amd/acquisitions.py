@@ -11,6 +11,7 @@ import warnings
 import numpy as np
 
 from . import _ffi
+from .utility import COMPILED_IN, device_thetas, inner_expectation
 
 
 def constant_cost_withGradients(x):
@@ -61,10 +62,29 @@ class AcquisitionBase(object):
         raise NotImplementedError('')
 
     # -- shared by the subclasses
+    _model_entry = "acq_linear"   # the model method that tells a bocf_amd.multi_outputGP from anything else
+
     def _device_model(self):
-        if not hasattr(self.model, "acq_linear"):
+        if not hasattr(self.model, self._model_entry):
             raise TypeError("bocf_amd acquisitions need a bocf_amd.multi_outputGP model (no CPU fallback)")
         return self.model
+
+    def _init_composite(self, cost_withGradients):
+        """Constructor tail of the composite-utility acquisitions (uEI_noiseless.py:25-38): W_samples, then -- without full
+        support -- ten utility parameters, in this order from np.random."""
+        if cost_withGradients is not None:
+            print('LBC acquisition does now make sense with cost. Cost set to constant.')
+        self.cost_withGradients = constant_cost_withGradients
+        self.n_attributes = self.model.output_dim
+        self.W_samples = np.random.normal(size=(25, self.n_attributes))          # uEI_noiseless.py:31
+        self.n_hyps_samples = min(10, self.model.number_of_hyps_samples())
+        self.use_full_support = self.utility.parameter_dist.use_full_support
+        if self.use_full_support:
+            self.utility_params_samples = self.utility.parameter_dist.support
+            self.utility_prob_dist = np.atleast_1d(self.utility.parameter_dist.prob_dist)
+        else:
+            self.utility_params_samples = self.utility.parameter_dist.sample(10)  # uEI_noiseless.py:38
+            self.utility_prob_dist = None
 
     def select_anchors(self, num_anchor=16):
         """Indices (into the last evaluated batch) of the `num_anchor` best candidates, computed on
@@ -90,32 +110,27 @@ class _ClosedForm(AcquisitionBase):
         self.use_full_support = self.utility.parameter_dist.use_full_support
         self.n_hyps_samples = min(10, self.model.number_of_hyps_samples())
 
-    def _compute_acq(self, X):
+    def _evaluate(self, X, n_theta_samples, entry):
+        """(X (n, d), what model.`entry` returns for it) with the support and its weights, or n_theta_samples freshly drawn thetas."""
         if self.use_full_support:
             self.utility_params_samples = self.utility.parameter_dist.support
             self.utility_param_dist = np.atleast_1d(self.utility.parameter_dist.prob_dist)
             prob = self.utility_param_dist
         else:
-            self.utility_params_samples = self.utility.parameter_dist.sample(self._n_theta_samples)
+            self.utility_params_samples = self.utility.parameter_dist.sample(n_theta_samples)
             prob = None
         X = np.atleast_2d(X)
         thetas = np.asarray(self.utility_params_samples, dtype=float).reshape(len(self.utility_params_samples), -1)
         # the h-loop of maEI.py:85-98 runs on the device (with fixed hyper-parameters its identical passes are one pass)
-        acqX = self._device_model().acq_linear(X, self._kind, thetas, prob, n_hyps=self.n_hyps_samples)
+        return X, getattr(self._device_model(), entry)(X, self._kind, thetas, prob, n_hyps=self.n_hyps_samples)
+
+    def _compute_acq(self, X):
+        X, acqX = self._evaluate(X, self._n_theta_samples, "acq_linear")
         return np.reshape(acqX, (X.shape[0], 1))
 
     def _compute_acq_withGradients(self, X):
         """maEI.py:57-78 / maPI.py:56-76: value and d/dX; not-full-support draws 3 thetas (both classes)."""
-        if self.use_full_support:
-            self.utility_params_samples = self.utility.parameter_dist.support
-            self.utility_param_dist = np.atleast_1d(self.utility.parameter_dist.prob_dist)
-            prob = self.utility_param_dist
-        else:
-            self.utility_params_samples = self.utility.parameter_dist.sample(3)
-            prob = None
-        X = np.atleast_2d(X)
-        thetas = np.asarray(self.utility_params_samples, dtype=float).reshape(len(self.utility_params_samples), -1)
-        acqX, dacq_dX = self._device_model().acq_linear_grad(X, self._kind, thetas, prob, n_hyps=self.n_hyps_samples)
+        X, (acqX, dacq_dX) = self._evaluate(X, 3, "acq_linear_grad")
         return np.reshape(acqX, (X.shape[0], 1)), np.reshape(dacq_dX, X.shape)
 
 
@@ -155,22 +170,7 @@ class _MonteCarlo(AcquisitionBase):
         self.optimizer = optimizer
         self.utility = utility
         super(_MonteCarlo, self).__init__(model, space, optimizer, cost_withGradients=cost_withGradients)
-        if cost_withGradients is not None:
-            print('LBC acquisition does now make sense with cost. Cost set to constant.')
-        self.cost_withGradients = constant_cost_withGradients
-        self.n_attributes = self.model.output_dim
-        self.W_samples = np.random.normal(size=(25, self.n_attributes))          # uEI_noiseless.py:31
-        self.n_hyps_samples = min(10, self.model.number_of_hyps_samples())
-        self.use_full_support = self.utility.parameter_dist.use_full_support
-        if self.use_full_support:
-            self.utility_params_samples = self.utility.parameter_dist.support
-            self.utility_prob_dist = np.atleast_1d(self.utility.parameter_dist.prob_dist)
-        else:
-            self.utility_params_samples = self.utility.parameter_dist.sample(10)  # uEI_noiseless.py:38
-
-    def _thetas(self):
-        s = np.asarray(self.utility_params_samples, dtype=float)
-        return s.reshape(len(self.utility_params_samples), -1)
+        self._init_composite(cost_withGradients)
 
     def _compute_acq(self, X, parallel=True):
         """`parallel` is accepted for signature compatibility: the reference's pathos variant
@@ -181,9 +181,7 @@ class _MonteCarlo(AcquisitionBase):
         if kind is None:
             return self._host_utility_acq(X)
         prob = self.utility_prob_dist if self.use_full_support else None
-        thetas = self._thetas()
-        if kind in (_ffi.UTIL_NEG_SUM_EXP, _ffi.UTIL_NEG_EXP_COS):
-            thetas = np.zeros((thetas.shape[0], 1))        # parameter unused by these utilities
+        thetas = device_thetas(kind, self.utility_params_samples)
         acqX = model.acq_mc(X, self._kind, kind, self.utility.device_params, thetas, prob, W=self.W_samples, n_hyps=self.n_hyps_samples,
                             program=self.utility.program_blob if kind == _ffi.UTIL_PROGRAM else None)
         return np.reshape(acqX, (X.shape[0], 1))
@@ -201,11 +199,8 @@ class _MonteCarlo(AcquisitionBase):
         kind = self._device_kind_or_none()
         if kind is None:
             return self._host_utility_acq_with_gradients(X, samples2, prob)
-        thetas = np.asarray(samples2, dtype=float).reshape(len(samples2), -1)
-        if kind in (_ffi.UTIL_NEG_SUM_EXP, _ffi.UTIL_NEG_EXP_COS):
-            thetas = np.zeros((thetas.shape[0], 1))
-        acqX, dacq_dX = self._device_model().acq_mc_grad(X, kind, self.utility.device_params, thetas, prob, W=self.W_samples,
-                                                         n_hyps=self.n_hyps_samples,
+        acqX, dacq_dX = self._device_model().acq_mc_grad(X, kind, self.utility.device_params, device_thetas(kind, samples2), prob,
+                                                         W=self.W_samples, n_hyps=self.n_hyps_samples,
                                                          program=self.utility.program_blob if kind == _ffi.UTIL_PROGRAM else None)
         return np.reshape(acqX, (X.shape[0], 1)), np.reshape(dacq_dX, X.shape)
 
@@ -221,7 +216,7 @@ class _MonteCarlo(AcquisitionBase):
                               "(mean, variance, gradients) is computed on the GPU, the Monte-Carlo loop over U runs on the HOST -- "
                               "orders of magnitude slower than a device utility (Utility(..., device=...); device='program' traces this "
                               "callable and runs it on the GPU)"
-                              % ", ".join(sorted(["linear", "neg_sq_dist", "neg_sum_exp", "neg_exp_cos", "rosenbrock"])), RuntimeWarning,
+                              % ", ".join(sorted(COMPILED_IN)), RuntimeWarning,
                               stacklevel=3)
                 self._warned_host_utility = True
             return None
@@ -352,62 +347,35 @@ class uKG(AcquisitionBase):
     when the utility's device kind has one, Monte-Carlo over W_samples otherwise.  A utility without a device kind raises
     NotImplementedError."""
     analytical_gradient_prediction = True
+    _model_entry = "acq_kg"
 
     def __init__(self, model, space, optimizer=None, cost_withGradients=None, utility=None, n_fantasies=16, n_ref_points=64):
         self.optimizer = optimizer
         self.utility = utility
         super(uKG, self).__init__(model, space, optimizer, cost_withGradients=cost_withGradients)
-        if cost_withGradients is not None:
-            print('LBC acquisition does now make sense with cost. Cost set to constant.')
-        self.cost_withGradients = constant_cost_withGradients
         if not 1 <= int(n_fantasies) <= 256:
             raise ValueError("n_fantasies must be in 1 .. 256")
         if not 1 <= int(n_ref_points) <= 1024:
             raise ValueError("n_ref_points must be in 1 .. 1024")
-        self.n_attributes = self.model.output_dim
         self.n_fantasies, self.n_ref_points = int(n_fantasies), int(n_ref_points)
-        self.Z_samples = np.random.normal(size=(self.n_fantasies, self.n_attributes))
-        self.W_samples = np.random.normal(size=(25, self.n_attributes))
-        self.n_hyps_samples = min(10, self.model.number_of_hyps_samples())
-        self.use_full_support = self.utility.parameter_dist.use_full_support
-        if self.use_full_support:
-            self.utility_params_samples = self.utility.parameter_dist.support
-            self.utility_prob_dist = np.atleast_1d(self.utility.parameter_dist.prob_dist)
-        else:
-            self.utility_params_samples = self.utility.parameter_dist.sample(10)
-            self.utility_prob_dist = None
+        self.Z_samples = np.random.normal(size=(self.n_fantasies, self.model.output_dim))
+        self._init_composite(cost_withGradients)
         self.reference_points = None          # the set in use
         self._user_reference_points = None
         self._staged_serial = None
 
     # ---- what the device evaluates
     def _mode_and_kind(self):
-        """(mode, device utility kind) as the recommendation step chooses its form (recommend.py)."""
-        from .recommend import _CLOSED_KINDS, _KIND_NAMES
-        m = self.model.output_dim
-        if self.utility.linear:
-            return _ffi.EU_MEAN, _ffi.UTIL_LINEAR
+        """(mode, device utility kind) as the recommendation step chooses its form (utility.inner_expectation)."""
         try:
-            kind = self.utility.device_kind(m)
+            mode, kind = inner_expectation(self.utility, self.model.output_dim)
         except NotImplementedError:
-            raise NotImplementedError("uKG needs a utility with a device kind (Utility(..., device=...): linear, neg_sq_dist, neg_sum_exp, "
-                                      "neg_exp_cos, rosenbrock): the look-ahead runs on the device, there is no host loop for a Python callable")
+            raise NotImplementedError("uKG needs a utility with a device kind (Utility(..., device=...): %s): the look-ahead runs on the "
+                                      "device, there is no host loop for a Python callable" % ", ".join(COMPILED_IN))
         if kind == _ffi.UTIL_PROGRAM:
             raise NotImplementedError("uKG does not take a utility program (Utility(..., device='program')): the knowledge gradient runs the "
-                                      "compiled-in utilities only (linear, neg_sq_dist, neg_sum_exp, neg_exp_cos, rosenbrock)")
-        name = _KIND_NAMES[kind]
-        if kind == _ffi.UTIL_LINEAR:
-            return _ffi.EU_MEAN, kind
-        if name in _CLOSED_KINDS and not (name == "rosenbrock" and m % 2):
-            return _ffi.EU_CLOSED, kind
-        return _ffi.EU_MC, kind
-
-    def _thetas(self, kind):
-        s = np.asarray(self.utility_params_samples, dtype=float)
-        thetas = s.reshape(len(self.utility_params_samples), -1)
-        if kind in (_ffi.UTIL_NEG_SUM_EXP, _ffi.UTIL_NEG_EXP_COS):
-            thetas = np.zeros((thetas.shape[0], 1))        # parameter unused by these utilities
-        return thetas
+                                      "compiled-in utilities only (%s)" % ", ".join(COMPILED_IN))
+        return mode, kind
 
     # ---- reference points
     def set_reference_points(self, A):
@@ -423,7 +391,7 @@ class uKG(AcquisitionBase):
             pts.append(np.atleast_2d(samples_multidimensional_uniform(_bounds_of(self.space), self.n_ref_points - 1)))
         # the training input with the best current expected utility  sum_l p_l E[U(theta_l, f(x))]
         Xt = np.atleast_2d(model.get_evaluated_points())
-        thetas = self._thetas(kind)
+        thetas = device_thetas(kind, self.utility_params_samples)
         L, n = thetas.shape[0], Xt.shape[0]
         Z = np.broadcast_to(self.W_samples, (L,) + self.W_samples.shape) if mode == _ffi.EU_MC else None
         v = model.expected_utility(np.tile(Xt, (L, 1)), mode, kind, thetas, np.repeat(np.arange(L), n), Z=Z, n_hyps=self.n_hyps_samples,
@@ -441,17 +409,13 @@ class uKG(AcquisitionBase):
             self._staged_serial = serial
         model.set_reference_points(self.reference_points)     # (free when this set is the resident one)
 
-    def _device_model(self):
-        if not hasattr(self.model, "acq_kg"):
-            raise TypeError("bocf_amd acquisitions need a bocf_amd.multi_outputGP model (no CPU fallback)")
-        return self.model
-
     def _evaluate(self, X, grad):
         X = np.atleast_2d(X)
         mode, kind = self._mode_and_kind()
         self._stage(mode, kind)
         prob = self.utility_prob_dist if self.use_full_support else None
-        out = self._device_model().acq_kg(X, mode, kind, self.utility.device_params, self._thetas(kind), prob, self.Z_samples,
+        thetas = device_thetas(kind, self.utility_params_samples)
+        out = self._device_model().acq_kg(X, mode, kind, self.utility.device_params, thetas, prob, self.Z_samples,
                                          W=self.W_samples if mode == _ffi.EU_MC else None, n_hyps=self.n_hyps_samples, grad=grad)
         return X, out
 

@@ -13,6 +13,24 @@ import numpy as np
 from . import _ffi
 from .hyper import OutputHyper
 from .kern import SE, kernel_spec
+from .utility import device_utility
+
+
+class _Resident(object):
+    """THE record of what the host believes is resident on the device -- a new resident buffer is a field here, and the events that
+    invalidate it name it in their forget() call; nowhere else.  None = unknown / not resident.
+    candidates: their count; W, Z, reference: key of the uploaded set_mc_samples / set_eu_samples / set_reference_points array;
+    program: the utility program blob; query, gradient: (key, arrays) of the last all-hyper-sample posterior query, served per h as
+    slices."""
+    __slots__ = ("candidates", "W", "Z", "program", "reference", "query", "gradient")
+
+    def __init__(self):
+        self.forget()
+
+    def forget(self, *names):
+        """Forget the named fields, or everything."""
+        for name in names or self.__slots__:
+            setattr(self, name, None)
 
 
 class _GPView(object):
@@ -115,13 +133,8 @@ class multi_outputGP(object):
         self._X = None
         self._Y = None
         self._fitted = False
-        self._cand_token = None
-        self._n_resident = None       # candidates resident on the device (unknown after a fit)
+        self._resident = _Resident()
         self._fit_key = None
-        self._W_key = None
-        self._prog_key = None
-        self._Z_key = None
-        self._ref_key = None          # reference set resident on the device (set_reference_points)
         self._cov_points = self._next_point = self._grad_point = None
         self.incremental = True       # O(N^2) updateModel when only targets change or one observation is appended
         # ---- hyper-parameter learning (fixed_hyps=False): GPModel's sampler settings (gpmodel.py:32)
@@ -138,7 +151,6 @@ class multi_outputGP(object):
         self._sampler_outputs = None                       # per output: parameter state of GPModel.model
         self._Ymat = None                                  # (m, N) targets, cached for the inferences of one update
         self._ibuf = None                                  # argument block of bocf_infer (arrays + ctypes pointers)
-        self._query_cache = self._grad_cache = None        # last all-hyper-sample posterior query (served per h as slices)
         self._fit_serial = 0
         self._instances = None                             # [h][j] -> (variance, lengthscale (d,), noise): GPModel.model_instances
         self._kernel_ids = None
@@ -154,13 +166,7 @@ class multi_outputGP(object):
         st = dict(self.__dict__)
         st["_ctx"] = None
         st["_fitted"] = False
-        st["_cand_token"] = None
-        st["_n_resident"] = None
-        st["_W_key"] = None
-        st["_prog_key"] = None
-        st["_Z_key"] = None
-        st["_ref_key"] = None
-        st["_query_cache"] = st["_grad_cache"] = None
+        st["_resident"] = _Resident()
         st["_ibuf"] = None
         return st
 
@@ -191,8 +197,7 @@ class multi_outputGP(object):
         if len(Y) != self.output_dim or any(y.shape[0] != X.shape[0] for y in Y):
             raise ValueError("Y_all must hold output_dim arrays of N observations")
         prevX = self._X
-        self._n_resident = None
-        self._ref_key = None          # every model change drops the device's reference set
+        self._resident.forget("candidates", "reference")      # every model change drops the device's reference set
         self._X, self._Y = X.copy(), [y[:, None].copy() for y in Y]
         self._Ymat = None
         self._ibuf = None
@@ -263,22 +268,22 @@ class multi_outputGP(object):
         jit, lml = np.zeros(M), np.zeros(M)
         rc = lib.bocf_fit(ctx.handle, _ffi.dptr(self._X), _ffi.dptr(Y), N, d, M, kid, _ffi.dptr(var), _ffi.dptr(ls), _ffi.dptr(noise), 5,
                           _ffi.dptr(jit), _ffi.dptr(lml))
-        _ffi.check(rc, "bocf_fit")
+        self._refactorized(rc, "bocf_fit", M)
+        return jit, lml
+
+    def _refactorized(self, rc, what, M=None):
+        """After every library call that factorizes anew (bocf_fit, bocf_infer, the HMC chains): the fit and the uploads that live with
+        it are gone.  With M, a positive return raises jitchol's error for the outputs that failed."""
+        _ffi.check(rc, what)
         self._fitted = False
-        self._W_key = None
-        self._prog_key = None
-        self._Z_key = None
-        self._cand_token = None
-        self._n_resident = None       # candidates resident on the device (unknown after a fit)
-        if rc > 0:   # jitchol gave up (GPy/util/linalg.py:71) for the outputs whose last rung still has a bad pivot
+        self._resident.forget("W", "Z", "program", "candidates")
+        if M is not None and rc > 0:   # jitchol gave up (GPy/util/linalg.py:71) for the outputs whose last rung still has a bad pivot
             err = np.linalg.LinAlgError("not positive definite, even with jitter.")
             err.outputs = self._failed_outputs(M)
             raise err
-        return jit, lml
 
     def _failed_outputs(self, M):
         """Outputs whose factorization failed in the last bocf_fit / bocf_infer (the library's own per-output info)."""
-        import ctypes
         info = (ctypes.c_int * M)()
         _ffi.check(_ffi.load().bocf_last_fit_info(self._context().handle, info, M), "bocf_last_fit_info")
         return [j for j in range(M) if info[j] != 0]
@@ -290,7 +295,7 @@ class multi_outputGP(object):
         self._fit_key = self._hyper_key()
         self._fitted = True
         self._fit_serial += 1
-        self._query_cache = self._grad_cache = None
+        self._resident.forget("query", "gradient")
 
     # ---- hyper-parameter learning: GPModel._create_model / updateModel (gpmodel.py:50-128) ------------------------
     def _create_sampler_state(self):
@@ -355,17 +360,7 @@ class multi_outputGP(object):
                 raise err
         self._send_kernel_ids(self._kernel_ids)             # (no-op unless the outputs differ in kernel family)
         rc = _ffi.load().bocf_infer(self._context().handle, *b["args"])
-        _ffi.check(rc, "bocf_infer")
-        self._fitted = False
-        self._W_key = None
-        self._prog_key = None
-        self._Z_key = None
-        self._cand_token = None
-        self._n_resident = None       # candidates resident on the device (unknown after a fit)
-        if rc > 0:   # jitchol gave up (GPy/util/linalg.py:71) for the outputs whose last rung still has a bad pivot
-            err = np.linalg.LinAlgError("not positive definite, even with jitter.")
-            err.outputs = self._failed_outputs(self.output_dim)
-            raise err
+        self._refactorized(rc, "bocf_infer", self.output_dim)
         return b["lml"].copy(), b["dv"].copy(), b["dl"].copy(), b["dn"].copy()
 
     def _update_hyper_samples(self):
@@ -440,18 +435,12 @@ class multi_outputGP(object):
                               fixed.ctypes.data_as(ip), pr.a, pr.b, _ffi.dptr(mom), _ffi.dptr(uni), ns, int(hmc_iters), float(stepsize), 5,
                               1 if raise_on_failure else 0, _ffi.dptr(chains), acc.ctypes.data_as(ip), div.ctypes.data_as(ip),
                               status.ctypes.data_as(ip), ctypes.byref(ninf))
-            _ffi.check(rc, "bocf_hmc")
+            self._refactorized(rc, "bocf_hmc")
         else:
             rc = lib.bocf_hmc_streamed(ctx.handle, _ffi.dptr(self._X), _ffi.dptr(self._Ymat), N, d, m, kid, _ffi.dptr(theta), nls,
                                        fixed.ctypes.data_as(ip), pr.a, pr.b, _ffi.dptr(mom), _ffi.dptr(uni), ns, int(hmc_iters), float(stepsize),
                                        _ffi.dptr(chains), acc.ctypes.data_as(ip), div.ctypes.data_as(ip), ctypes.byref(done), ctypes.byref(ninf))
-            _ffi.check(rc, "bocf_hmc_streamed")
-        self._fitted = False
-        self._W_key = None
-        self._prog_key = None
-        self._Z_key = None
-        self._cand_token = None
-        self._n_resident = None       # candidates resident on the device (unknown after a fit)
+            self._refactorized(rc, "bocf_hmc_streamed")
         for j, o in enumerate(outs):
             o.param_array[:] = theta[j]
         out_chains = [chains[j, :, :int(np.sum(~outs[j].fixed))].copy() for j in range(m)]
@@ -493,31 +482,35 @@ class multi_outputGP(object):
         X = _ffi.f64(X)
         if X.ndim != 2 or X.shape[1] != self._X.shape[1]:
             raise ValueError("candidates must be (n, %d)" % self._X.shape[1])
-        self._n_resident = None
+        self._resident.forget("candidates")
         _ffi.check(_ffi.load().bocf_set_candidates(self._context().handle, _ffi.dptr(X), X.shape[0]), "bocf_set_candidates")
-        self._n_resident = X.shape[0]
+        self._resident.candidates = X.shape[0]
         return X.shape[0]
 
+    def _all_hyper_samples(self, slot, key, X, run):
+        """A posterior query at X: `run(n)` makes the device call for the n staged candidates and returns its (H * m, n, ...) arrays.
+        cbo.py walks the hyper-samples with set_hyperparameters(h) + a posterior query per h (cbo.py:162-166,176-178): the device
+        answers for all H at once, so the queries after the first are slices of the same pass, kept in self._resident.`slot`."""
+        if self._H == 1:
+            return run(self._set_candidates(X))
+        self._ensure_fitted()
+        key = key + (np.shape(X), hash(np.ascontiguousarray(X, dtype=np.float64).tobytes()), self._fit_serial)
+        hit = getattr(self._resident, slot)
+        if hit is None or hit[0] != key:
+            hit = (key, run(self._set_candidates(X)))
+            setattr(self._resident, slot, hit)
+        rows = self._rows()
+        return tuple(None if a is None else a[rows].copy() for a in hit[1])
+
     def _predict(self, X, flags, want_var=True):
-        key = None
-        if self._H > 1:
-            # cbo.py walks the hyper-samples with set_hyperparameters(h) + a posterior query per h (cbo.py:162-166,176-178):
-            # the device answers for all H at once, so the queries after the first are slices of the same pass
-            self._ensure_fitted()
-            key = ("p", flags, want_var, np.shape(X), hash(np.ascontiguousarray(X, dtype=np.float64).tobytes()), self._fit_serial)
-            if self._query_cache is not None and self._query_cache[0] == key:
-                mean, var = self._query_cache[1]
-                return mean[self._rows()].copy(), (var[self._rows()].copy() if want_var else None)
-        n = self._set_candidates(X)
-        M = self.output_dim * self._H
-        mean = np.empty((M, n))
-        var = np.empty((M, n)) if want_var else None
-        if n:
-            _ffi.check(_ffi.load().bocf_predict(self._context().handle, flags, _ffi.dptr(mean), _ffi.dptr(var)), "bocf_predict")
-        if self._H > 1:
-            self._query_cache = (key, (mean, var))
-            return mean[self._rows()].copy(), (var[self._rows()].copy() if want_var else None)
-        return mean, var
+        def run(n):
+            M = self.output_dim * self._H
+            mean = np.empty((M, n))
+            var = np.empty((M, n)) if want_var else None
+            if n:
+                _ffi.check(_ffi.load().bocf_predict(self._context().handle, flags, _ffi.dptr(mean), _ffi.dptr(var)), "bocf_predict")
+            return mean, var
+        return self._all_hyper_samples("query", ("p", flags, want_var), X, run)
 
     def predict(self, X, full_cov=False):
         """Posterior means and variances at X, likelihood noise included, clipped at 1e-10
@@ -559,23 +552,13 @@ class multi_outputGP(object):
         return out[self._rows()].copy() if self._H > 1 else out
 
     def _gradients(self, X):
-        key = None
-        if self._H > 1:
-            self._ensure_fitted()
-            key = ("g", np.shape(X), hash(np.ascontiguousarray(np.atleast_2d(X), dtype=np.float64).tobytes()), self._fit_serial)
-            if self._grad_cache is not None and self._grad_cache[0] == key:
-                dmean, dvar = self._grad_cache[1]
-                return dmean[self._rows()].copy(), dvar[self._rows()].copy()
-        n = self._set_candidates(np.atleast_2d(X))
-        d = self._X.shape[1]
-        M = self.output_dim * self._H
-        dmean, dvar = np.empty((M, n, d)), np.empty((M, n, d))
-        if n:
-            _ffi.check(_ffi.load().bocf_predict_gradients(self._context().handle, _ffi.dptr(dmean), _ffi.dptr(dvar)), "bocf_predict_gradients")
-        if self._H > 1:
-            self._grad_cache = (key, (dmean, dvar))
-            return dmean[self._rows()].copy(), dvar[self._rows()].copy()
-        return dmean, dvar
+        def run(n):
+            shape = (self.output_dim * self._H, n, self._X.shape[1])
+            dmean, dvar = np.empty(shape), np.empty(shape)
+            if n:
+                _ffi.check(_ffi.load().bocf_predict_gradients(self._context().handle, _ffi.dptr(dmean), _ffi.dptr(dvar)), "bocf_predict_gradients")
+            return dmean, dvar
+        return self._all_hyper_samples("gradient", ("g",), np.atleast_2d(X), run)
 
     def posterior_mean_gradient(self, X):
         """d mu / dX, (m, n, d)  (multi_outputGP.py:284-294 -> gp.py:438-461)."""
@@ -610,11 +593,11 @@ class multi_outputGP(object):
         self._ensure_fitted()
         A = self._points(A, "the reference points")
         key = (A.shape, hash(A.tobytes()), self._fit_serial)
-        if key == getattr(self, "_ref_key", None):
+        if key == self._resident.reference:
             return
-        self._ref_key = None
+        self._resident.forget("reference")
         _ffi.check(_ffi.load().bocf_set_ref_points(self._context().handle, _ffi.dptr(A), A.shape[0]), "bocf_set_ref_points")
-        self._ref_key = key
+        self._resident.reference = key
 
     def _staged(self, name, what):
         P = getattr(self, name, None)
@@ -706,10 +689,9 @@ class multi_outputGP(object):
         "closed" or "mc" (or the _ffi.EU_* value) is the inner expectation, Zf (Sf, m) the fantasy normals, W (S, m) the common random
         numbers of the "mc" mode.  Returns KG (n,), or (KG (n,), dKG/dX (n, d)) with grad=True.  The values stay on the device for
         select_topk (fetch=False returns None)."""
-        modes = {"mean": _ffi.EU_MEAN, "closed": _ffi.EU_CLOSED, "mc": _ffi.EU_MC}
-        mode = modes[mode] if isinstance(mode, str) else int(mode)
+        mode = _ffi.eu_mode(mode)
         self._begin_acq(n_hyps, True)
-        if getattr(self, "_ref_key", None) is None or self._ref_key[2] != self._fit_serial:
+        if self._resident.reference is None or self._resident.reference[2] != self._fit_serial:
             raise RuntimeError("no reference points resident for this fit: call set_reference_points")
         if mode == _ffi.EU_MC:
             if W is None:
@@ -719,16 +701,12 @@ class multi_outputGP(object):
         Zf = _ffi.f64(np.atleast_2d(Zf))
         if Zf.shape[1] != self.output_dim:
             raise ValueError("Zf must be (Sf, output_dim)")
-        th = _ffi.f64(np.atleast_2d(thetas))
-        L, tdim = th.shape
-        params = None if util_params is None else _ffi.f64(np.atleast_1d(util_params))
-        prob = None if prob is None else _ffi.f64(np.atleast_1d(prob))
+        util = self._utility_args(util_params, thetas, prob)
         acq = np.empty(n) if fetch else None
         dacq = np.empty((n, self._X.shape[1])) if grad else None
         if n:
-            _ffi.check(_ffi.load().bocf_acq_kg(self._context().handle, mode, int(util_kind), _ffi.dptr(params), 0 if params is None else params.size,
-                                               _ffi.dptr(th), tdim, _ffi.dptr(prob), L, _ffi.dptr(Zf), Zf.shape[0], _ffi.dptr(acq), _ffi.dptr(dacq)),
-                       "bocf_acq_kg")
+            _ffi.check(_ffi.load().bocf_acq_kg(self._context().handle, mode, int(util_kind), *util, _ffi.dptr(Zf), Zf.shape[0], _ffi.dptr(acq),
+                                               _ffi.dptr(dacq)), "bocf_acq_kg")
         return (acq, dacq) if grad else acq
 
     # ---- joint posterior and composite Thompson sampling ------------------------------------------------------------------------
@@ -800,12 +778,11 @@ class multi_outputGP(object):
             self._posterior_samples(g, Zg, keep_out=False)
             order += [s for h in hs for s in np.flatnonzero(path_groups == h)]
         order = np.asarray(order, dtype=int)
-        th = _ffi.f64(thetas[order])
-        pa = None if params is None else _ffi.f64(np.atleast_1d(params))
+        pa, n_pa, th, tdim, _, _ = self._utility_args(params, thetas[order], None)
         idx = np.empty((P, k), dtype=np.int64)
         val = np.empty((P, k))
-        _ffi.check(_ffi.load().bocf_thompson_select(self._context().handle, kind, _ffi.dptr(pa), 0 if pa is None else pa.size, _ffi.dptr(th), th.shape[1],
-                                                    int(k), idx.ctypes.data_as(_ffi._c_ll_p), _ffi.dptr(val)), "bocf_thompson_select")
+        _ffi.check(_ffi.load().bocf_thompson_select(self._context().handle, kind, pa, n_pa, th, tdim, int(k), idx.ctypes.data_as(_ffi._c_ll_p),
+                                                    _ffi.dptr(val)), "bocf_thompson_select")
         out_idx, out_val = np.empty_like(idx), np.empty_like(val)
         out_idx[order], out_val[order] = idx, val
         return out_idx, out_val
@@ -885,8 +862,18 @@ class multi_outputGP(object):
         ctx.set_option("best_group", -1 if own_best else self._current_h)
         self._current_h = n_h - 1
 
-    def acq_linear(self, X, kind, thetas, prob, n_hyps=None):
-        """Closed-form EI/PI of theta.f over the batch X on the device (bocf_acq_linear)."""
+    @staticmethod
+    def _utility_args(util_params, thetas, prob):
+        """The utility block of the library's argument lists, in their order: (params, n_util_params, thetas, theta_dim, prob, L) from
+        util_params (any shape or None), thetas (L, theta_dim) (None: L = 1, theta_dim = 0) and the weights prob (L,) or None.  The
+        pointers keep their arrays alive."""
+        params = None if util_params is None else _ffi.f64(np.atleast_1d(util_params))
+        th = None if thetas is None else _ffi.f64(np.atleast_2d(thetas))
+        L, tdim = (1, 0) if th is None else th.shape
+        prob = None if prob is None else _ffi.f64(np.atleast_1d(prob))
+        return _ffi.dptr(params), 0 if params is None else params.size, _ffi.dptr(th), tdim, _ffi.dptr(prob), L
+
+    def _acq_linear(self, X, kind, thetas, prob, n_hyps, grad):
         self._begin_acq(n_hyps, True)
         n = self._set_candidates(np.atleast_2d(X))
         thetas = _ffi.f64(np.atleast_2d(thetas))
@@ -894,24 +881,20 @@ class multi_outputGP(object):
             raise ValueError("theta must have output_dim entries")
         prob = None if prob is None else _ffi.f64(np.atleast_1d(prob))
         acq = np.empty(n)
+        dacq = np.empty((n, self._X.shape[1])) if grad else None
+        what = "bocf_acq_linear_grad" if grad else "bocf_acq_linear"
+        out = (_ffi.dptr(acq), _ffi.dptr(dacq)) if grad else (_ffi.dptr(acq),)
         if n:
-            _ffi.check(_ffi.load().bocf_acq_linear(self._context().handle, kind, _ffi.dptr(thetas), _ffi.dptr(prob), thetas.shape[0],
-                                                   _ffi.dptr(acq)), "bocf_acq_linear")
-        return acq
+            _ffi.check(getattr(_ffi.load(), what)(self._context().handle, kind, _ffi.dptr(thetas), _ffi.dptr(prob), thetas.shape[0], *out), what)
+        return (acq, dacq) if grad else acq
+
+    def acq_linear(self, X, kind, thetas, prob, n_hyps=None):
+        """Closed-form EI/PI of theta.f over the batch X on the device (bocf_acq_linear)."""
+        return self._acq_linear(X, kind, thetas, prob, n_hyps, False)
 
     def acq_linear_grad(self, X, kind, thetas, prob, n_hyps=None):
         """(acq (n,), d acq/dX (n, d)) of the closed-form EI/PI (bocf_acq_linear_grad)."""
-        self._begin_acq(n_hyps, True)
-        n = self._set_candidates(np.atleast_2d(X))
-        thetas = _ffi.f64(np.atleast_2d(thetas))
-        if thetas.shape[1] != self.output_dim:
-            raise ValueError("theta must have output_dim entries")
-        prob = None if prob is None else _ffi.f64(np.atleast_1d(prob))
-        acq, dacq = np.empty(n), np.empty((n, self._X.shape[1]))
-        if n:
-            _ffi.check(_ffi.load().bocf_acq_linear_grad(self._context().handle, kind, _ffi.dptr(thetas), _ffi.dptr(prob), thetas.shape[0],
-                                                        _ffi.dptr(acq), _ffi.dptr(dacq)), "bocf_acq_linear_grad")
-        return acq, dacq
+        return self._acq_linear(X, kind, thetas, prob, n_hyps, True)
 
     def set_utility_program(self, blob):
         """Stage a utility program (the blob of utility_program.Program.to_bytes(), Utility.program_blob) on the device for the calls
@@ -920,10 +903,10 @@ class multi_outputGP(object):
         if blob is None:
             raise ValueError("utility kind 'program' needs the program blob (Utility(..., device='program').program_blob)")
         blob = bytes(blob)
-        if blob == self._prog_key:
+        if blob == self._resident.program:
             return
         _ffi.check(_ffi.load().bocf_set_utility_program(self._context().handle, blob, len(blob)), "bocf_set_utility_program")
-        self._prog_key = blob
+        self._resident.program = blob
 
     def acq_mc_grad(self, X, util_kind, util_params, thetas, prob, W=None, n_hyps=None, program=None):
         """(acq (n,), d acq/dX (n, d)) of the Monte-Carlo EI (bocf_acq_mc_grad); `program`: the blob for utility kind UTIL_PROGRAM."""
@@ -933,14 +916,10 @@ class multi_outputGP(object):
         if W is not None:
             self.set_mc_samples(W)
         n = self._set_candidates(np.atleast_2d(X))
-        params = None if util_params is None else _ffi.f64(np.atleast_1d(util_params))
-        th = _ffi.f64(np.atleast_2d(thetas))
-        L, tdim = th.shape
-        prob = None if prob is None else _ffi.f64(np.atleast_1d(prob))
+        util = self._utility_args(util_params, thetas, prob)
         acq, dacq = np.empty(n), np.empty((n, self._X.shape[1]))
         if n:
-            _ffi.check(_ffi.load().bocf_acq_mc_grad(self._context().handle, util_kind, _ffi.dptr(params), 0 if params is None else params.size,
-                                                    _ffi.dptr(th), tdim, _ffi.dptr(prob), L, _ffi.dptr(acq), _ffi.dptr(dacq)), "bocf_acq_mc_grad")
+            _ffi.check(_ffi.load().bocf_acq_mc_grad(self._context().handle, util_kind, *util, _ffi.dptr(acq), _ffi.dptr(dacq)), "bocf_acq_mc_grad")
         return acq, dacq
 
     def set_mc_samples(self, W):
@@ -949,10 +928,10 @@ class multi_outputGP(object):
         if W.shape[1] != self.output_dim:
             raise ValueError("W must be (S, output_dim)")
         key = (W.shape, hash(W.tobytes()))
-        if key == self._W_key:       # the same common random numbers are already resident (L-BFGS calls f_df hundreds of times)
+        if key == self._resident.W:       # the same common random numbers are already resident (L-BFGS calls f_df hundreds of times)
             return
         _ffi.check(_ffi.load().bocf_set_mc_samples(self._context().handle, _ffi.dptr(W), W.shape[0]), "bocf_set_mc_samples")
-        self._W_key = key
+        self._resident.W = key
 
     def acq_mc(self, X, kind, util_kind, util_params, thetas, prob, W=None, fetch=True, n_hyps=None, program=None):
         """Monte-Carlo EI/PI of a device utility over the batch X (bocf_acq_mc); `program`: the blob for utility kind UTIL_PROGRAM."""
@@ -965,18 +944,10 @@ class multi_outputGP(object):
         return self._acq_mc_resident(kind, util_kind, util_params, thetas, prob, n, fetch)
 
     def _acq_mc_resident(self, kind, util_kind, util_params, thetas, prob, n, fetch=True):
-        lib, ctx = _ffi.load(), self._context()
-        params = None if util_params is None else _ffi.f64(np.atleast_1d(util_params))
-        if thetas is None:
-            th, L, tdim = None, 1, 0
-        else:
-            th = _ffi.f64(np.atleast_2d(thetas))
-            L, tdim = th.shape
-        prob = None if prob is None else _ffi.f64(np.atleast_1d(prob))
+        util = self._utility_args(util_params, thetas, prob)
         acq = np.empty(n) if (fetch and n is not None) else None
         if n is None or n > 0:
-            _ffi.check(lib.bocf_acq_mc(ctx.handle, kind, util_kind, _ffi.dptr(params), 0 if params is None else params.size, _ffi.dptr(th),
-                                       tdim, _ffi.dptr(prob), L, _ffi.dptr(acq)), "bocf_acq_mc")
+            _ffi.check(_ffi.load().bocf_acq_mc(self._context().handle, kind, util_kind, *util, _ffi.dptr(acq)), "bocf_acq_mc")
         return acq
 
     def set_eu_samples(self, Z):
@@ -989,10 +960,10 @@ class multi_outputGP(object):
         if Z.ndim != 3 or Z.shape[2] != self.output_dim:
             raise ValueError("Z must be (L, S, output_dim)")
         key = (Z.shape, hash(Z.tobytes()))
-        if key == self._Z_key:
+        if key == self._resident.Z:
             return
         _ffi.check(_ffi.load().bocf_set_eu_samples(self._context().handle, _ffi.dptr(Z), Z.shape[0], Z.shape[1]), "bocf_set_eu_samples")
-        self._Z_key = key
+        self._resident.Z = key
 
     def expected_utility(self, X, mode, utility, thetas, row_param, Z=None, n_hyps=None, grad=False, util_params=None):
         """Posterior expected utility of the recommendation step (cbo.py:121-235) on the device, all utility parameters in one call:
@@ -1009,8 +980,7 @@ class multi_outputGP(object):
         n_hyps: hyper-samples to sum (default min(10, number_of_hyps_samples())); more than are resident is an IndexError; with fixed
         hyper-parameters the one resident sample counts n_hyps times, as the reference's identical passes do.  thetas must be 2-D.  Leaves the model on hyper-sample n_hyps - 1, as the
         reference's set_hyperparameters(h) loop does.  Returns v (n,), or (v (n,), dv/dX (n, d)) with grad=True."""
-        modes = {"mean": _ffi.EU_MEAN, "closed": _ffi.EU_CLOSED, "mc": _ffi.EU_MC}
-        mode = modes[mode] if isinstance(mode, str) else int(mode)
+        mode = _ffi.eu_mode(mode)
         self._ensure_fitted()
         if hasattr(utility, "device_kind"):
             kind = 0 if mode == _ffi.EU_MEAN else utility.device_kind(self.output_dim)
@@ -1019,8 +989,7 @@ class multi_outputGP(object):
             if kind == _ffi.UTIL_PROGRAM and mode == _ffi.EU_MC:
                 self.set_utility_program(utility.program_blob)
         elif isinstance(utility, str):
-            from .utility import _DEVICE_KINDS
-            kind = _DEVICE_KINDS[utility]
+            kind = device_utility(utility).kind
         else:
             kind = 0 if utility is None else int(utility)
         n_h = min(10, self.number_of_hyps_samples()) if n_hyps is None else int(n_hyps)
@@ -1032,7 +1001,6 @@ class multi_outputGP(object):
         th = _ffi.f64(thetas)
         if th.ndim != 2:
             raise ValueError("thetas must be 2-D (L, theta_dim); write L scalar parameters as an (L, 1) array")
-        L, tdim = th.shape
         rows = np.ascontiguousarray(np.asarray(row_param).reshape(-1), dtype=np.int32)
         if mode == _ffi.EU_MC:
             if Z is None:
@@ -1042,18 +1010,18 @@ class multi_outputGP(object):
             n = self._set_candidates(np.atleast_2d(X))
             if n != rows.size:
                 raise ValueError("row_param must hold one parameter index per row of X")
-        elif self._n_resident is None or self._n_resident != rows.size:
+        elif self._resident.candidates is None or self._resident.candidates != rows.size:
             # the library reads row_param and writes the outputs for every RESIDENT candidate: the sizes must agree
             raise ValueError("X = None evaluates the resident candidates (%s): row_param must hold one index per candidate, it holds %d"
-                             % ("none known" if self._n_resident is None else self._n_resident, rows.size))
+                             % ("none known" if self._resident.candidates is None else self._resident.candidates, rows.size))
         n = rows.size
-        params = None if util_params is None else _ffi.f64(np.atleast_1d(util_params))
+        params, n_params, th, tdim, _, L = self._utility_args(util_params, th, None)
         val = np.empty(n)
         dval = np.empty((n, self._X.shape[1])) if grad else None
         if n:
-            _ffi.check(_ffi.load().bocf_expected_utility(self._context().handle, mode, kind, _ffi.dptr(params), 0 if params is None else params.size,
-                                                         _ffi.dptr(th), tdim, L, rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), n_h,
-                                                         _ffi.dptr(val), _ffi.dptr(dval)), "bocf_expected_utility")
+            _ffi.check(_ffi.load().bocf_expected_utility(self._context().handle, mode, kind, params, n_params, th, tdim, L,
+                                                         rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), n_h, _ffi.dptr(val), _ffi.dptr(dval)),
+                       "bocf_expected_utility")
         if not self.fixed_hyps:
             self._current_h = min(n_h, self._H) - 1
         return (val, dval) if grad else val

@@ -27,11 +27,9 @@ import numpy as np
 
 from . import _ffi
 from .acquisition_optimizer import _bounds_of, lbfgsb_batched, samples_multidimensional_uniform
+from .utility import device_utility, expectation_mode
 
 N_Z_SAMPLES = 50                  # cbo.py:200
-_CLOSED_KINDS = ("neg_sq_dist", "neg_sum_exp", "rosenbrock")
-_KIND_NAMES = {_ffi.UTIL_LINEAR: "linear", _ffi.UTIL_NEG_SQ_DIST: "neg_sq_dist", _ffi.UTIL_NEG_SUM_EXP: "neg_sum_exp",
-               _ffi.UTIL_NEG_EXP_COS: "neg_exp_cos", _ffi.UTIL_ROSENBROCK: "rosenbrock", _ffi.UTIL_PROGRAM: "program"}
 
 
 def branch_of(utility, expectation_utility=None):
@@ -79,11 +77,12 @@ def recognise_expectation_utility(expectation_utility, utility, m, theta=None):
     Like Utility._recognise: psi and its gradient are probed at fixed points drawn from a private RNG (the global np.random
     stream is not touched) and compared with the closed form of the utility's own device kind."""
     try:
-        kind = _KIND_NAMES[utility.device_kind(m)]
+        kind = utility.device_kind(m)
     except NotImplementedError:
         return None
-    if kind not in _CLOSED_KINDS or (kind == "rosenbrock" and m % 2):
+    if expectation_mode(kind, m) != _ffi.EU_CLOSED:
         return None
+    kind = device_utility(kind).name
     if theta is None:
         support = getattr(utility.parameter_dist, "support", None)
         if support is None or len(support) == 0:
@@ -110,7 +109,7 @@ def device_evaluator(model, branch, utility, parameters, Z=None, n_hyps=None, ki
     """ev(X, rows, grad) -> (v (n,), dv/dX (n, d) or None): sum_h E_h[U(theta_{rows[i]}, f(X_i))] from bocf_expected_utility."""
     thetas = np.asarray(parameters, dtype=float).reshape(len(parameters), -1)
     if kind is None and branch != "mean":
-        kind = _KIND_NAMES[utility.device_kind(model.output_dim)]
+        kind = device_utility(utility.device_kind(model.output_dim)).name
 
     def ev(X, rows, grad=False):
         # (a utility program travels with its Utility: the model stages the blob)
@@ -231,7 +230,7 @@ def make_evaluator(model, branch, utility, parameters, expectation_utility=None,
         kind = recognise_expectation_utility(expectation_utility, utility, model.output_dim, parameters[0])
     else:
         try:
-            kind = _KIND_NAMES[utility.device_kind(model.output_dim)]
+            kind = device_utility(utility.device_kind(model.output_dim)).name
         except NotImplementedError:
             kind = None
     if kind is not None:

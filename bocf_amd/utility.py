@@ -3,6 +3,7 @@
 DEVICE specification of the utility: the Monte-Carlo acquisitions evaluate U on the GPU, so U
 is one of the closed set of utilities the reference's experiment scripts use, or -- on request,
 device="program" -- the user's own callable traced into a utility program (utility_program.py)."""
+import collections
 import pickle
 
 import numpy as np
@@ -44,8 +45,50 @@ class ExpectationUtility(object):
         self.gradient = gradient
 
 
-_DEVICE_KINDS = {"linear": _ffi.UTIL_LINEAR, "neg_sq_dist": _ffi.UTIL_NEG_SQ_DIST, "neg_sum_exp": _ffi.UTIL_NEG_SUM_EXP,
-                 "neg_exp_cos": _ffi.UTIL_NEG_EXP_COS, "rosenbrock": _ffi.UTIL_ROSENBROCK, "program": _ffi.UTIL_PROGRAM}
+# THE table of the device utilities -- a new one is a row here (and its code on the device), nothing else on the host: name, _ffi id,
+# `closed`: for which output counts m the device has a closed-form expectation (None: for none), `reads_theta`: False when the
+# utility ignores its parameter (the device is then sent zeros (L, 1)).
+DeviceUtility = collections.namedtuple("DeviceUtility", "name kind closed reads_theta")
+DEVICE_UTILITIES = (
+    DeviceUtility("linear", _ffi.UTIL_LINEAR, None, True),                  # (its expectation is the utility of the posterior mean)
+    DeviceUtility("neg_sq_dist", _ffi.UTIL_NEG_SQ_DIST, lambda m: True, True),
+    DeviceUtility("neg_sum_exp", _ffi.UTIL_NEG_SUM_EXP, lambda m: True, False),
+    DeviceUtility("neg_exp_cos", _ffi.UTIL_NEG_EXP_COS, None, False),
+    DeviceUtility("rosenbrock", _ffi.UTIL_ROSENBROCK, lambda m: m % 2 == 0, True),
+    DeviceUtility("program", _ffi.UTIL_PROGRAM, None, True),
+)
+_DEVICE_KINDS = {u.name: u.kind for u in DEVICE_UTILITIES}
+_ROW_OF = {key: u for u in DEVICE_UTILITIES for key in (u.name, u.kind)}
+COMPILED_IN = tuple(u.name for u in DEVICE_UTILITIES if u.kind != _ffi.UTIL_PROGRAM)
+
+
+def device_utility(which):
+    """The table row of a device utility given by name or by _ffi.UTIL_* value."""
+    return _ROW_OF[which]
+
+
+def expectation_mode(kind, m):
+    """How the device takes E[U(theta, f)] of utility `kind` under a posterior with m outputs: the posterior mean (_ffi.EU_MEAN) for the
+    linear utility, the closed form (EU_CLOSED) where the table has one for this m, Monte-Carlo (EU_MC) otherwise."""
+    u = device_utility(kind)
+    if u.kind == _ffi.UTIL_LINEAR:
+        return _ffi.EU_MEAN
+    return _ffi.EU_CLOSED if u.closed is not None and u.closed(m) else _ffi.EU_MC
+
+
+def inner_expectation(utility, m):
+    """(mode, device kind) of the inner expectation of `utility`, as the recommendation step and the knowledge gradient choose it.
+    NotImplementedError (from Utility.device_kind) when the utility has no device kind."""
+    if utility.linear:
+        return _ffi.EU_MEAN, _ffi.UTIL_LINEAR
+    kind = utility.device_kind(m)
+    return expectation_mode(kind, m), kind
+
+
+def device_thetas(kind, samples):
+    """The utility parameters as the device wants them: (L, theta_dim), or zeros (L, 1) for a utility that does not read theta."""
+    thetas = np.asarray(samples, dtype=float).reshape(len(samples), -1)
+    return thetas if device_utility(kind).reads_theta else np.zeros((thetas.shape[0], 1))
 
 
 def _host_func(kind, params):
