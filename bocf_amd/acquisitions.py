@@ -318,6 +318,85 @@ class uEI_noiseless(_MonteCarlo):
     _kind = _ffi.ACQ_EI
 
 
+class uEI_pending(uEI_noiseless):
+    """uEI_noiseless conditioned on the pending points of a batch under construction: with P = (p_1 .. p_r), r <= 15, set,
+
+        alpha(x | P) = sum_l p_l (1/S) sum_s max( U(theta_l, y_s(x)) - max(best_l, max_i U(theta_l, F_s(p_i))), 0 ),
+
+    where (F_s, y_s(x)) is a joint posterior sample at (P, x): F_s from the normals Z (S, m, r) of set_pending_points, y_s(x) correlated
+    with it through Sigma(P, x) and closed with W_samples[s] -- so alpha(x | P) = qEI(P u {x}) - qEI(P) for these normals, the increment a
+    greedy batch maximises (CompositeGreedyBatch).  Everything runs on the device (bocf_acq_pending).  Unlike the parent it uses the latent,
+    noiseless variance.  With no pending points (None or an empty P) the class IS its parent: the same calls, the same numbers.
+
+    Parameter conventions are the parent's: _compute_acq uses utility_params_samples (the support with its weights, or the ten parameters
+    drawn at construction), _compute_acq_withGradients the support or ONE freshly drawn parameter per call.  The pending points are staged
+    again whenever the model's fit serial changes.  A utility without a compiled-in device kind raises NotImplementedError."""
+    _model_entry = "acq_pending"
+
+    def __init__(self, *a, **kw):
+        super(uEI_pending, self).__init__(*a, **kw)
+        self.pending_points = None
+        self.pending_Z = None
+        self._staged_serial = None
+
+    def set_pending_points(self, P, Z=None):
+        """P (r, d), 1 <= r <= 15, and the joint normals Z (S, m, r), S = len(W_samples); Z = None draws np.random.normal(size=(S, m, r)).
+        P = None or an empty P clears the pending set: the parent's behaviour, exactly."""
+        if P is None or np.size(P) == 0:
+            self.pending_points = self.pending_Z = self._staged_serial = None
+            return
+        P = np.array(np.atleast_2d(P), dtype=float)
+        if not 1 <= P.shape[0] <= 15:
+            raise ValueError("1 .. 15 pending points")
+        S, m = self.W_samples.shape
+        Z = np.random.normal(size=(S, m, P.shape[0])) if Z is None else np.array(Z, dtype=float)
+        if Z.shape != (S, m, P.shape[0]):
+            raise ValueError("Z must be (len(W_samples), output_dim, r) = %r" % ((S, m, P.shape[0]),))
+        self.pending_points, self.pending_Z, self._staged_serial = P, Z, None
+
+    def _pending_kind(self):
+        try:
+            kind = self.utility.device_kind(self.model.output_dim)
+        except NotImplementedError:
+            kind = None
+        if kind is None or kind == _ffi.UTIL_PROGRAM:
+            raise NotImplementedError("uEI_pending needs a utility with a compiled-in device kind (Utility(..., device=...): %s): the "
+                                      "conditioning on pending points runs on the device, there is no host loop and no utility program"
+                                      % ", ".join(COMPILED_IN))
+        return kind
+
+    def _stage(self):
+        model = self._device_model()
+        model._ensure_fitted()
+        self._staged_serial = model._fit_serial
+        model.set_pending_points(self.pending_points, self.pending_Z, W=self.W_samples)     # (free when this set is the resident one)
+
+    def _compute_acq(self, X, parallel=True):
+        if self.pending_points is None:
+            return super(uEI_pending, self)._compute_acq(X, parallel)
+        X = np.atleast_2d(X)
+        kind = self._pending_kind()
+        self._stage()
+        prob = self.utility_prob_dist if self.use_full_support else None
+        acqX = self._device_model().acq_pending(X, kind, self.utility.device_params, device_thetas(kind, self.utility_params_samples), prob,
+                                                W=self.W_samples, n_hyps=self.n_hyps_samples)
+        return np.reshape(acqX, (X.shape[0], 1))
+
+    def _compute_acq_withGradients(self, X):
+        if self.pending_points is None:
+            return super(uEI_pending, self)._compute_acq_withGradients(X)
+        X = np.atleast_2d(X)
+        if self.use_full_support:
+            samples2, prob = self.utility.parameter_dist.support, self.utility_prob_dist
+        else:
+            samples2, prob = self.utility.parameter_dist.sample(1), None
+        kind = self._pending_kind()
+        self._stage()
+        acqX, dacq_dX = self._device_model().acq_pending(X, kind, self.utility.device_params, device_thetas(kind, samples2), prob,
+                                                         W=self.W_samples, n_hyps=self.n_hyps_samples, grad=True)
+        return np.reshape(acqX, (X.shape[0], 1)), np.reshape(dacq_dX, X.shape)
+
+
 class uPI(_MonteCarlo):
     analytical_gradient_prediction = False
     _kind = _ffi.ACQ_PI

@@ -68,6 +68,45 @@ class CompositeThompsonBatch(object):
         return np.vstack((x0, Xc[distinct_picks(idx)]))
 
 
+class CompositeGreedyBatch(object):
+    """q <= 16 suggestions per iteration by greedily maximising the joint Monte-Carlo expected improvement of the composite utility
+    (q-uEI): point k maximises alpha(x | p_1 .. p_{k-1}) = qEI({p_1 .. p_{k-1}, x}) - qEI({p_1 .. p_{k-1}}) with the earlier points
+    pending.  `acquisition` is a bocf_amd.uEI_pending.  The first point is acquisition.optimize's with no pending point, as in Sequential
+    (batch_size = 1 is Sequential).  Draws from np.random, in this order: whatever the optimisation of point 1 draws, then ONE
+    np.random.normal(size=(S, m, q - 1)) for the whole batch (S = len(acquisition.W_samples)), then whatever the optimisations of points
+    2 .. q draw.  Step k uses the pending points found so far and the leading k - 1 columns of that array: the joint sample at the
+    pending points is mu(P) + L z with L the lower Cholesky factor of Sigma(P, P) + tau I, whose leading block does not change when a
+    point is appended, so the samples at the earlier pending points stay fixed across the steps of a batch (up to the jitter tau, 1e-8
+    of the mean variance of the pending points, which is recomputed per step).  The pending points are cleared at the end, also when a
+    step raises."""
+
+    def __init__(self, acquisition, batch_size):
+        if not 1 <= int(batch_size) <= 16:
+            raise ValueError("batch_size must be in 1 .. 16")
+        if not hasattr(acquisition, "set_pending_points"):
+            raise TypeError("CompositeGreedyBatch needs an acquisition with set_pending_points (bocf_amd.uEI_pending)")
+        self.acquisition = acquisition
+        self.batch_size = int(batch_size)
+
+    def compute_batch(self, duplicate_manager=None, context_manager=None, x_baseline=None):
+        acq, q = self.acquisition, self.batch_size
+        acq.set_pending_points(None)
+        try:
+            x, _ = acq.optimize(duplicate_manager=duplicate_manager, x_baseline=x_baseline)
+            X = np.atleast_2d(x)
+            if q == 1:
+                return X
+            S, m = acq.W_samples.shape
+            Z = np.random.normal(size=(S, m, q - 1))
+            for k in range(1, q):
+                acq.set_pending_points(X, np.ascontiguousarray(Z[:, :, :k]))
+                x, _ = acq.optimize(duplicate_manager=duplicate_manager, x_baseline=x_baseline)
+                X = np.vstack((X, np.atleast_2d(x)))
+            return X
+        finally:
+            acq.set_pending_points(None)
+
+
 def distinct_picks(idx):
     """Row s of idx ranks path s's candidates; path s takes its first candidate that no earlier path took."""
     taken = []

@@ -194,6 +194,12 @@ struct bocf_ctx {
   int kg_na = 0;             // reference points resident (0 = none)
   DevBuf kg_XA, kg_VA, kg_Wa, kg_muA, kg_s2A, kg_nug;
   DevBuf kg_V, kg_W, kg_cov, kg_s2c, kg_dcov, kg_dmean, kg_dvar, kg_par, kg_v0, kg_astar, kg_AB, kg_out, kg_dout;
+  // ---- pending points of a greedy batch (capi_pending.hip): the r <= 15 points P staged like a reference set in buffers of their own
+  // (the uKG reference set survives), Q = (Sigma(P, P) + tau I)^-1 (m, r, r) and the joint samples F, G (m, r, S) made on the host
+  // (pending_host.h).  The per-chunk workspaces are the look-ahead's (kg_V, kg_cov, kg_s2c, kg_W, kg_dmean, kg_dvar, kg_dcov, kg_dout).
+  int pd_r = 0, pd_S = 0;    // pending points resident (0 = none) and the samples F, G were made for
+  DevBuf pd_XP, pd_VP, pd_Wp, pd_muP, pd_cov, pd_pack, pd_QFG, pd_par, pd_best, pd_T, pd_muc, pd_E;
+  std::vector<double> pd_host, pd_up;   // Sigma(P, P) | mu(P) as copied back; Q | F | G as uploaded (kept: the upload is asynchronous)
 };
 
 // util_prog.hip: what every entry point checks before it evaluates the resident program (utility kind BOCF_UTIL_PROGRAM): one is resident,
@@ -203,6 +209,14 @@ int bocf_check_resident_program(bocf_ctx* c, const char* who, int m, int theta_d
 void bocf_thompson_drop(bocf_ctx* c);
 // the resident reference set belongs to one posterior: dropped by every fit and data change (NOT by a candidate upload)
 void bocf_kg_drop(bocf_ctx* c);
+// the resident pending points belong to one posterior, like the reference set: dropped wherever it is
+void bocf_pending_drop(bocf_ctx* c);
+// capi_kg.hip, shared with capi_pending.hip.  A staged point set of the look-ahead paths: the uKG reference set or the pending points.
+struct KgRefSet { const DevBuf* XA; const DevBuf* VA; const DevBuf* Wa; int na; };
+int bocf_kg_stage(bocf_ctx* c, const double* Xdev, int na, int nap, double* VA, double* Wa, double* muA, double* s2A);
+int bocf_kg_chunk_size(const bocf_ctx* c, int mg);      // candidates per chunk under option workspace_mb; below 128: refuse
+int bocf_kg_chunk(bocf_ctx* c, const KgRefSet& ref, int j0, int mg, int c0, int cn, int cnp, bool with_grad, double* mu);
+int bocf_kg_chunk_dcov(bocf_ctx* c, const KgRefSet& ref, int j0, int mg, int c0, int cn, int a0, int an);
 // capi_thompson.hip, shared with capi_kg.hip: the argument checks of the joint-posterior entry points (errors name `who`) and
 // V = R^T K(X, Xq) for the mg outputs from j0 (Np x npad per output, k-major) with, for mu != nullptr, the posterior mean at Xq (mg x npad)
 int bocf_check_posterior(bocf_ctx* c, const char* who);

@@ -433,3 +433,32 @@ struct KgGradArgs {
   double* dacq; int accumulate; double scale;       // (C, d)
 };
 void launch_kg_grad(const KgGradArgs& a, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------
+// Monte-Carlo improvement of the composite utility conditioned on pending points (pending.hip)
+// ---------------------------------------------------------------------------------------
+// out = Sigma_j(P, P) of every output (m, r, r; from the padded tiles, row stride ldc) followed by mu_j(P) (m, r): one block for the one host copy
+void launch_pending_pack(const double* cov, long ldc, long strideC, const double* mu, long ldmu, int r, double* out, int m, hipStream_t s);
+struct PendArgs {
+  const double* cov; int ldc; long strideC;         // Sigma_j(x_c, p_i): (m, rows, ldc) of one hyper-sample, C x r valid
+  const double* s2c; const double* muc; int lds;    // raw sigma^2_j(x_c) and mu_j(x_c): (m, lds)
+  const double* Q;                                  // (m, r, r): Sigma~_j^-1
+  const double* F; const double* G;                 // (m, r, S): joint samples at the pending points and L^-T z, s fastest
+  const double* Wt;                                 // (m, S) transposed common random numbers
+  const double* best;                               // (L) best-so-far of this hyper-sample
+  double* T;                                        // (L, S) thresholds of this hyper-sample (launch_pending_threshold writes, the others read)
+  const double* theta; int theta_dim; const double* prob; int L;
+  const double* util_params;                        // (BOCF_MAX_M)
+  int m, r, S, C, util_kind;
+  double* acq; int accumulate; double scale;        // (C): written, or added to (hyper-sample h > 0)
+  // gradient form
+  const double* dmu; const double* ds2; int ldg;    // d mu_j / dx, d sigma^2_j / dx: (m, ldg, d)
+  const double* dcov;                               // d Sigma_j(x_c, p_i) / dx_c: (m, C, r, d)
+  double* E;                                        // (C, m, S) scratch: every lane reads back what it wrote itself
+  int d; double* dacq;                              // (C, d)
+};
+// bytes of LDS the tables of a value launch need (G, W, T, theta, prob, utility parameters); in LDS up to 64 KiB, else read from memory
+size_t pending_table_bytes(const PendArgs& a);
+void launch_pending_threshold(const PendArgs& a, hipStream_t s);
+void launch_pending_acq(const PendArgs& a, hipStream_t s);
+void launch_pending_grad(const PendArgs& a, hipStream_t s);

@@ -110,7 +110,8 @@ extern "C" void bocf_destroy(bocf_ctx* c) {
                     &c->gval, &c->shard_meta, &c->chol_flags, &c->eu_theta, &c->eu_rows, &c->eu_Z, &c->eu_val, &c->eu_grad,
                     &c->ts_X, &c->ts_K, &c->ts_V, &c->ts_mp, &c->ts_mu, &c->ts_Z, &c->ts_jit, &c->ts_u, &c->ts_theta, &c->ts_params, &c->ts_out,
                     &c->kg_XA, &c->kg_VA, &c->kg_Wa, &c->kg_muA, &c->kg_s2A, &c->kg_nug, &c->kg_V, &c->kg_W, &c->kg_cov, &c->kg_s2c, &c->kg_dcov, &c->kg_dmean, &c->kg_dvar,
-                    &c->kg_par, &c->kg_v0, &c->kg_astar, &c->kg_AB, &c->kg_out, &c->kg_dout, &c->prog_buf};
+                    &c->kg_par, &c->kg_v0, &c->kg_astar, &c->kg_AB, &c->kg_out, &c->kg_dout, &c->prog_buf,
+                    &c->pd_XP, &c->pd_VP, &c->pd_Wp, &c->pd_muP, &c->pd_cov, &c->pd_pack, &c->pd_QFG, &c->pd_par, &c->pd_best, &c->pd_T, &c->pd_muc, &c->pd_E};
   for (DevBuf* b : bufs) b->release();
   if (c->infer_out) (void)hipHostFree(c->infer_out);
   if (c->tile_ctr) (void)hipFree(c->tile_ctr);
@@ -255,6 +256,7 @@ extern "C" int bocf_set_posterior(bocf_ctx* c, int m, int C, int N, const double
   c->m = m; c->N = N; c->Np = round_up(N, BOCF_TILE); c->d = 1; c->C = C; c->pred_cap = cap;
   bocf_thompson_drop(c);
   bocf_kg_drop(c);
+  bocf_pending_drop(c);
   c->fitted = true;
   c->canned = true;
   c->have_acq = false;

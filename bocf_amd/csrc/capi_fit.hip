@@ -74,6 +74,7 @@ static int begin_model(bocf_ctx* c, const FitInput& in) {
   c->fitted = false; c->canned = false; c->sharded = false; c->have_acq = false; c->r32_valid = false; c->ri8_valid = false;
   bocf_thompson_drop(c);
   bocf_kg_drop(c);
+  bocf_pending_drop(c);
   c->N = in.N; c->Np = round_up(in.N, BOCF_TILE); c->d = in.d; c->m = in.m; c->kernel_id = in.kernel_id;
   c->xs_stride = (long)c->Np * in.d;
   return take_kernel_ids(c, in.m);
@@ -559,6 +560,7 @@ static int refresh_targets(bocf_ctx* c, const double* Y, double* lml_out) {
   const int Np = c->Np, m = c->m;
   bocf_thompson_drop(c);
   bocf_kg_drop(c);
+  bocf_pending_drop(c);
   const std::vector<double> yc = centre_targets(c, Y, c->N, Np, m);
   HIPCHK(hipMemcpyAsync(c->hypd.p, c->hyp.data(), sizeof(KernHyp) * m, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(c->yc.p, yc.data(), sizeof(double) * (size_t)m * Np, hipMemcpyHostToDevice, c->stream));
@@ -595,6 +597,7 @@ extern "C" int bocf_append(bocf_ctx* c, const double* x_new, const double* Y, do
   c->C = 0;                                            // the resident candidate batch is replaced
   bocf_thompson_drop(c);
   bocf_kg_drop(c);
+  bocf_pending_drop(c);
   HIPCHK(hipMemcpyAsync(c->Xc.p, x_new, sizeof(double) * d, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemsetAsync(c->info.p, 0, sizeof(int) * m, c->stream));
   // k(X, x_new) as column 0 of a 128-wide K* block, u = R^T k, ||u||^2, w = R u

@@ -12,6 +12,8 @@
 
 void bocf_kg_drop(bocf_ctx* c) { c->kg_na = 0; }
 
+static KgRefSet kg_ref(bocf_ctx* c) { return KgRefSet{&c->kg_XA, &c->kg_VA, &c->kg_Wa, c->kg_na}; }
+
 static int kg_ready(bocf_ctx* c, const char* who) {
   if (bocf_check_posterior(c, who)) return -1;
   if (c->kg_na < 1) return fail(who, "no reference points: call bocf_set_ref_points after the fit");
@@ -23,7 +25,7 @@ static int kg_ready(bocf_ctx* c, const char* who) {
 static const char* kWorkspace = "the look-ahead workspace exceeds option workspace_mb: fewer candidates or a larger cap";
 
 // candidates per chunk: V of a chunk (mg x Np x chunk doubles) stays under the cap; 0 when not even 128 fit
-static int kg_chunk_size(const bocf_ctx* c, int mg) {
+int bocf_kg_chunk_size(const bocf_ctx* c, int mg) {
   const double cap = (double)c->workspace_mb * 1048576.0;
   const double per_col = (double)mg * (double)c->Np * sizeof(double);
   long cols = (long)(cap / per_col) / BOCF_TILE * BOCF_TILE;
@@ -44,10 +46,22 @@ static void kg_enqueue_W(bocf_ctx* c, int j0, int mg, const double* V, int npad,
   launch_gemm_f64(w, mg, 0, c->stream);
 }
 
-// V, Sigma(., A) and the raw sigma^2 of candidates [c0, c0 + cn) for the mg outputs from j0 into kg_V (Np x cnp), kg_cov (cnp x nap), kg_s2c (cnp);
-// with_grad: also W = Ky^-1 k(X, x_c) and d mu / dx, d sigma^2 / dx into kg_dmean / kg_dvar (cnp x d)
-static int kg_chunk(bocf_ctx* c, int j0, int mg, int c0, int cn, int cnp, bool with_grad) {
-  const int Np = c->Np, d = c->d, na = c->kg_na, nap = round_up(na, BOCF_TILE);
+// What staging a point set A (na points resident at Xdev, nap = na rounded up to 128) enqueues for all M outputs: V_A = R^T K(X, A), Wa = Ky^-1 K(X, A),
+// mu(A) and (s2A != nullptr) the raw sigma^2(A).  Shared by bocf_set_ref_points and bocf_set_pending_points, each with buffers of its own.
+int bocf_kg_stage(bocf_ctx* c, const double* Xdev, int na, int nap, double* VA, double* Wa, double* muA, double* s2A) {
+  const int M = c->m, Np = c->Np;
+  PhaseTimer t(c, "kg_ref");
+  if (bocf_enqueue_V(c, 0, M, Xdev, na, nap, VA, muA)) return -1;
+  kg_enqueue_W(c, 0, M, VA, nap, Wa);
+  if (s2A) launch_kg_diag(VA, nap, (long)Np * nap, Np, na, c->hypd.as<KernHyp>(), s2A, nap, M, c->stream);
+  return 0;
+}
+
+// V, Sigma(., A) and the raw sigma^2 of candidates [c0, c0 + cn) for the mg outputs from j0 into kg_V (Np x cnp), kg_cov (cnp x nap), kg_s2c (cnp),
+// against the staged set `ref`; with_grad: also W = Ky^-1 k(X, x_c) and d mu / dx, d sigma^2 / dx into kg_dmean / kg_dvar (cnp x d);
+// mu != nullptr: also the posterior mean of the candidates (mg x cnp)
+int bocf_kg_chunk(bocf_ctx* c, const KgRefSet& ref, int j0, int mg, int c0, int cn, int cnp, bool with_grad, double* mu) {
+  const int Np = c->Np, d = c->d, na = ref.na, nap = round_up(na, BOCF_TILE);
   const double* Xq = c->Xc.as<double>() + (size_t)c0 * d;
   const int* kids = BOCF_KIDS(c);
   if (c->kg_V.ensure(sizeof(double) * (size_t)mg * Np * cnp) || c->kg_cov.ensure(sizeof(double) * (size_t)mg * cnp * nap) ||
@@ -55,11 +69,11 @@ static int kg_chunk(bocf_ctx* c, int j0, int mg, int c0, int cn, int cnp, bool w
     return -1;
   {
     PhaseTimer t(c, "kg_V");
-    if (bocf_enqueue_V(c, j0, mg, Xq, cn, cnp, c->kg_V.as<double>(), nullptr)) return -1;
+    if (bocf_enqueue_V(c, j0, mg, Xq, cn, cnp, c->kg_V.as<double>(), mu)) return -1;
   }
   {
     PhaseTimer t(c, "kg_cov");
-    launch_post_cov(c->kg_V.as<double>(), cnp, (long)Np * cnp, c->kg_VA.as<double>() + (size_t)j0 * Np * nap, nap, (long)Np * nap, Xq, cn, c->kg_XA.as<double>(),
+    launch_post_cov(c->kg_V.as<double>(), cnp, (long)Np * cnp, ref.VA->as<double>() + (size_t)j0 * Np * nap, nap, (long)Np * nap, Xq, cn, ref.XA->as<double>(),
                     na, d, Np, c->kernel_id, kids ? kids + j0 : nullptr, c->hypd.as<KernHyp>() + j0, nullptr, 0, c->kg_cov.as<double>(), nap,
                     (long)cnp * nap, mg, c->stream);
     launch_kg_diag(c->kg_V.as<double>(), cnp, (long)Np * cnp, Np, cn, c->hypd.as<KernHyp>() + j0, c->kg_s2c.as<double>(), cnp, mg, c->stream);
@@ -78,13 +92,13 @@ static int kg_chunk(bocf_ctx* c, int j0, int mg, int c0, int cn, int cnp, bool w
 }
 
 // d Sigma(x_c, a) / dx_c of the chunk's cn candidates against reference points [a0, a0 + an) into kg_dcov (mg, cn, an, d)
-static int kg_chunk_dcov(bocf_ctx* c, int j0, int mg, int c0, int cn, int a0, int an) {
-  const int Np = c->Np, d = c->d, nap = round_up(c->kg_na, BOCF_TILE);
+int bocf_kg_chunk_dcov(bocf_ctx* c, const KgRefSet& ref, int j0, int mg, int c0, int cn, int a0, int an) {
+  const int Np = c->Np, d = c->d, nap = round_up(ref.na, BOCF_TILE);
   if (c->kg_dcov.ensure(sizeof(double) * (size_t)mg * cn * an * d)) return -1;
   const int* kids = BOCF_KIDS(c);
   PhaseTimer t(c, "kg_grad");
   launch_cov_grad(c->Xs.as<double>() + (long)j0 * c->xs_stride, c->xs_stride, c->N, d, c->kernel_id, kids ? kids + j0 : nullptr, c->hypd.as<KernHyp>() + j0,
-                  c->Xc.as<double>() + (size_t)c0 * d, cn, c->kg_XA.as<double>(), a0, an, c->kg_Wa.as<double>() + (size_t)j0 * Np * nap, nap, (long)Np * nap,
+                  c->Xc.as<double>() + (size_t)c0 * d, cn, ref.XA->as<double>(), a0, an, ref.Wa->as<double>() + (size_t)j0 * Np * nap, nap, (long)Np * nap,
                   c->kg_dcov.as<double>(), mg, c->stream);
   return 0;
 }
@@ -107,12 +121,7 @@ extern "C" int bocf_set_ref_points(bocf_ctx* c, const double* Xa, int na) {
   for (int j = 0; j < M; ++j) nug[j] = c->hyp[j].noise + 1e-8 + (j < (int)c->jitter.size() ? c->jitter[j] : 0.0);
   HIPCHK(hipMemcpyAsync(c->kg_XA.p, Xa, sizeof(double) * (size_t)na * d, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(c->kg_nug.p, nug.data(), sizeof(double) * (size_t)M, hipMemcpyHostToDevice, c->stream));
-  {
-    PhaseTimer t(c, "kg_ref");
-    if (bocf_enqueue_V(c, 0, M, c->kg_XA.as<double>(), na, nap, c->kg_VA.as<double>(), c->kg_muA.as<double>())) return -1;
-    kg_enqueue_W(c, 0, M, c->kg_VA.as<double>(), nap, c->kg_Wa.as<double>());
-    launch_kg_diag(c->kg_VA.as<double>(), nap, (long)Np * nap, Np, na, c->hypd.as<KernHyp>(), c->kg_s2A.as<double>(), nap, M, c->stream);
-  }
+  if (bocf_kg_stage(c, c->kg_XA.as<double>(), na, nap, c->kg_VA.as<double>(), c->kg_Wa.as<double>(), c->kg_muA.as<double>(), c->kg_s2A.as<double>())) return -1;
   HIPCHK(hipStreamSynchronize(c->stream));
   LAUNCHCHK();
   c->kg_na = na;
@@ -126,18 +135,18 @@ extern "C" int bocf_cov_to_ref(bocf_ctx* c, int group, double* cov_out, double* 
   int j0, mg, per;
   if (bocf_group_range(c, who, group, &j0, &mg, &per)) return -1;
   const int C = c->C, d = c->d, na = c->kg_na, nap = round_up(na, BOCF_TILE);
-  const int chunk = kg_chunk_size(c, mg);
+  const int chunk = bocf_kg_chunk_size(c, mg);
   if (chunk < BOCF_TILE) return fail(who, kWorkspace);
   if (dcov_out && (double)mg * C * (double)na * d * sizeof(double) > (double)c->workspace_mb * 1048576.0) return fail(who, kWorkspace);
   HIPCHK(hipSetDevice(c->device));
   for (int c0 = 0; c0 < C; c0 += chunk) {
     const int cn = C - c0 < chunk ? C - c0 : chunk, cnp = round_up(cn, BOCF_TILE);
-    if (kg_chunk(c, j0, mg, c0, cn, cnp, false)) return -1;
+    if (bocf_kg_chunk(c, kg_ref(c), j0, mg, c0, cn, cnp, false, nullptr)) return -1;
     for (int j = 0; j < mg; ++j)
       HIPCHK(hipMemcpy2DAsync(cov_out + ((size_t)j * C + c0) * na, sizeof(double) * na, c->kg_cov.as<double>() + (size_t)j * cnp * nap, sizeof(double) * nap,
                               sizeof(double) * na, cn, hipMemcpyDeviceToHost, c->stream));
     if (dcov_out) {
-      if (kg_chunk_dcov(c, j0, mg, c0, cn, 0, na)) return -1;
+      if (bocf_kg_chunk_dcov(c, kg_ref(c), j0, mg, c0, cn, 0, na)) return -1;
       for (int j = 0; j < mg; ++j)
         HIPCHK(hipMemcpyAsync(dcov_out + ((size_t)j * C + c0) * na * d, c->kg_dcov.as<double>() + (size_t)j * cn * na * d, sizeof(double) * (size_t)cn * na * d,
                               hipMemcpyDeviceToHost, c->stream));
@@ -156,14 +165,14 @@ extern "C" int bocf_conditioned_variance(bocf_ctx* c, int group, int q, double* 
   int j0, mg, per;
   if (bocf_group_range(c, who, group, &j0, &mg, &per)) return -1;
   const int C = c->C, d = c->d, nap = round_up(c->kg_na, BOCF_TILE);
-  const int chunk = kg_chunk_size(c, mg);
+  const int chunk = bocf_kg_chunk_size(c, mg);
   if (chunk < BOCF_TILE) return fail(who, kWorkspace);
   HIPCHK(hipSetDevice(c->device));
   const bool grad = dvar_out != nullptr;
   for (int c0 = 0; c0 < C; c0 += chunk) {
     const int cn = C - c0 < chunk ? C - c0 : chunk, cnp = round_up(cn, BOCF_TILE);
-    if (kg_chunk(c, j0, mg, c0, cn, cnp, grad)) return -1;
-    if (grad && kg_chunk_dcov(c, j0, mg, c0, cn, q, 1)) return -1;
+    if (bocf_kg_chunk(c, kg_ref(c), j0, mg, c0, cn, cnp, grad, nullptr)) return -1;
+    if (grad && bocf_kg_chunk_dcov(c, kg_ref(c), j0, mg, c0, cn, q, 1)) return -1;
     if (c->kg_out.ensure(sizeof(double) * (size_t)mg * cn) || (grad && c->kg_dout.ensure(sizeof(double) * (size_t)mg * cn * d))) return -1;
     launch_cond_var(c->kg_cov.as<double>(), nap, (long)cnp * nap, q, c->kg_s2c.as<double>(), cnp, c->kg_s2A.as<double>() + (size_t)j0 * nap, nap,
                     c->kg_nug.as<double>() + j0, grad ? c->kg_dvar.as<double>() : nullptr, cnp, grad ? c->kg_dcov.as<double>() : nullptr, cn, d,
@@ -209,7 +218,7 @@ extern "C" int bocf_acq_kg(bocf_ctx* c, int mode, int util_kind, const double* u
   mg = Ha * m;
   const int C = c->C, d = c->d, na = c->kg_na, nap = round_up(na, BOCF_TILE);
   const bool grad = dacq_out != nullptr;
-  int chunk = kg_chunk_size(c, mg);
+  int chunk = bocf_kg_chunk_size(c, mg);
   if (chunk < BOCF_TILE) return fail(who, kWorkspace);
   if (grad) {
     // one chunk: d Sigma / dx of every (candidate, reference point) is held at once (the optimiser's small batches)
@@ -244,8 +253,8 @@ extern "C" int bocf_acq_kg(bocf_ctx* c, int mode, int util_kind, const double* u
   }
   for (int c0 = 0; c0 < C; c0 += chunk) {
     const int cn = C - c0 < chunk ? C - c0 : chunk, cnp = round_up(cn, BOCF_TILE);
-    if (kg_chunk(c, 0, mg, c0, cn, cnp, grad)) return -1;
-    if (grad && kg_chunk_dcov(c, 0, mg, c0, cn, 0, na)) return -1;
+    if (bocf_kg_chunk(c, kg_ref(c), 0, mg, c0, cn, cnp, grad, nullptr)) return -1;
+    if (grad && bocf_kg_chunk_dcov(c, kg_ref(c), 0, mg, c0, cn, 0, na)) return -1;
     for (int h = 0; h < Ha; ++h) {
       KgArgs k = a;
       k.cov = c->kg_cov.as<double>() + (size_t)h * m * cnp * nap; k.strideC = (long)cnp * nap;

@@ -19,10 +19,10 @@ from .utility import device_utility
 class _Resident(object):
     """THE record of what the host believes is resident on the device -- a new resident buffer is a field here, and the events that
     invalidate it name it in their forget() call; nowhere else.  None = unknown / not resident.
-    candidates: their count; W, Z, reference: key of the uploaded set_mc_samples / set_eu_samples / set_reference_points array;
-    program: the utility program blob; query, gradient: (key, arrays) of the last all-hyper-sample posterior query, served per h as
+    candidates: their count; W, Z, reference, pending: key of the uploaded set_mc_samples / set_eu_samples / set_reference_points /
+    set_pending_points arrays; program: the utility program blob; query, gradient: (key, arrays) of the last all-hyper-sample posterior query, served per h as
     slices."""
-    __slots__ = ("candidates", "W", "Z", "program", "reference", "query", "gradient")
+    __slots__ = ("candidates", "W", "Z", "program", "reference", "pending", "query", "gradient")
 
     def __init__(self):
         self.forget()
@@ -148,6 +148,7 @@ class multi_outputGP(object):
         self._current_h = 0                                # set_hyperparameters(h)
         self.sample_jitter_tries = 10                      # rungs of the jitter ladder of the joint posterior samples
         self.last_sample_jitter = None                     # the jitter per output of the last posterior_samples_f / thompson_topk draw
+        self.last_pending_jitter = None                    # the jitter per output of the last set_pending_points
         self._sampler_outputs = None                       # per output: parameter state of GPModel.model
         self._Ymat = None                                  # (m, N) targets, cached for the inferences of one update
         self._ibuf = None                                  # argument block of bocf_infer (arrays + ctypes pointers)
@@ -197,7 +198,7 @@ class multi_outputGP(object):
         if len(Y) != self.output_dim or any(y.shape[0] != X.shape[0] for y in Y):
             raise ValueError("Y_all must hold output_dim arrays of N observations")
         prevX = self._X
-        self._resident.forget("candidates", "reference")      # every model change drops the device's reference set
+        self._resident.forget("candidates", "reference", "pending")      # every model change drops the device's reference set and pending points
         self._X, self._Y = X.copy(), [y[:, None].copy() for y in Y]
         self._Ymat = None
         self._ibuf = None
@@ -707,6 +708,59 @@ class multi_outputGP(object):
         if n:
             _ffi.check(_ffi.load().bocf_acq_kg(self._context().handle, mode, int(util_kind), *util, _ffi.dptr(Zf), Zf.shape[0], _ffi.dptr(acq),
                                                _ffi.dptr(dacq)), "bocf_acq_kg")
+        return (acq, dacq) if grad else acq
+
+    # ---- pending points of a greedy batch -------------------------------------------------------------------------------------
+    def set_pending_points(self, P, Zp, W=None):
+        """Stage the pending points P (r, d), 1 <= r <= 15, of a batch under construction for ALL hyper-samples (bocf_set_pending_points)
+        with the joint normals Zp (S, output_dim, r): the device keeps Q = (Sigma(P, P) + tau I)^-1 and the joint samples at P.  S must be
+        the number of resident Monte-Carlo samples (W (S, output_dim) is uploaded first when given).  The set stays resident until it is
+        replaced or the model changes -- the reference set of set_reference_points is not touched; re-sending the resident set is free.
+        The jitter tau per output is kept in last_pending_jitter."""
+        self._ensure_fitted()
+        if W is not None:
+            self.set_mc_samples(W)
+        P = self._points(P, "the pending points")
+        Zp = _ffi.f64(Zp)
+        if Zp.ndim != 3 or Zp.shape[1:] != (self.output_dim, P.shape[0]):
+            raise ValueError("Zp must be (S, output_dim, r)")
+        key = (P.shape, hash(P.tobytes()), Zp.shape, hash(Zp.tobytes()), self._fit_serial)
+        if key == self._resident.pending:
+            return
+        self._resident.forget("pending")
+        jit = np.empty(self.output_dim * self._H)
+        rc = _ffi.check(_ffi.load().bocf_set_pending_points(self._context().handle, _ffi.dptr(P), P.shape[0], _ffi.dptr(Zp), Zp.shape[0],
+                                                            self.sample_jitter_tries, _ffi.dptr(jit)), "bocf_set_pending_points")
+        self.last_pending_jitter = jit
+        if rc > 0:
+            raise np.linalg.LinAlgError("covariance of the pending points of output %d not positive definite, even with jitter %g" % (rc - 1, jit[rc - 1]))
+        self._resident.pending = key
+
+    def pending_samples(self):
+        """The joint samples F at the resident pending points, (H * output_dim, r, S) (bocf_get_pending_samples)."""
+        if self._resident.pending is None or self._resident.pending[4] != self._fit_serial:
+            raise RuntimeError("no pending points resident for this fit: call set_pending_points")
+        (r, _), (S, _, _) = self._resident.pending[0], self._resident.pending[2]
+        F = np.empty((self.output_dim * self._H, r, S))
+        _ffi.check(_ffi.load().bocf_get_pending_samples(self._context().handle, _ffi.dptr(F)), "bocf_get_pending_samples")
+        return F
+
+    def acq_pending(self, X, util_kind, util_params, thetas, prob, W=None, n_hyps=None, grad=False, fetch=True):
+        """Monte-Carlo expected improvement of the batch X (n, d) conditioned on the resident pending points (bocf_acq_pending):
+        alpha(x | P) = qEI(P u {x}) - qEI(P) for the staged normals; W (S, output_dim) are the common random numbers of the Monte-Carlo
+        acquisitions.  The best-so-far is that of acq_mc: the hyper-sample current on entry.  Returns alpha (n,), or
+        (alpha (n,), d alpha / dX (n, d)) with grad=True.  The values stay on the device for select_topk (fetch=False returns None)."""
+        self._begin_acq(n_hyps, False)
+        if self._resident.pending is None or self._resident.pending[4] != self._fit_serial:
+            raise RuntimeError("no pending points resident for this fit: call set_pending_points")
+        if W is not None:
+            self.set_mc_samples(W)
+        n = self._set_candidates(np.atleast_2d(X))
+        util = self._utility_args(util_params, thetas, prob)
+        acq = np.empty(n) if fetch else None
+        dacq = np.empty((n, self._X.shape[1])) if grad else None
+        if n:
+            _ffi.check(_ffi.load().bocf_acq_pending(self._context().handle, int(util_kind), *util, _ffi.dptr(acq), _ffi.dptr(dacq)), "bocf_acq_pending")
         return (acq, dacq) if grad else acq
 
     # ---- joint posterior and composite Thompson sampling ------------------------------------------------------------------------

@@ -422,6 +422,37 @@ int bocf_conditioned_variance(bocf_ctx* ctx, int group, int q, double* var_out, 
 int bocf_acq_kg(bocf_ctx* ctx, int mode, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim,
                 const double* prob, int L, const double* Zf, int Sf, double* acq_out, double* dacq_out);
 
+/* ---- greedy q-point batches: the Monte-Carlo expected improvement of the composite utility conditioned on pending points.  A batch
+ * is filled one point at a time with the earlier points pending (the way the method of cbo.py:274-281 is run with an evaluator of batch
+ * size q; the joint samples come from the look-ahead covariances of multi_outputGP.py:257-266 -> gp.py:576-583).  Per output j of
+ * hyper-sample h, with mu_j, sigma^2_j and Sigma_j as above and the pending points P = (p_1 .. p_r), 1 <= r <= 15:
+ *   Sigma~_j = Sigma_j(P, P) + tau_j I = L_j L_j^T (lower),  Q_j = Sigma~_j^-1          tau_j from the jitter ladder of the joint samples:
+ *                                                                                      1e-8 max(mean diag, 1e-10), x 10 per rung
+ *   F_sj = mu_j(P) + L_j Zp[s, j, :],  G_sj = L_j^-T Zp[s, j, :]                        Zp (S, m, r): host normals
+ *   c_j(x) = Sigma_j(P, x),  v_j(x) = max(sigma^2_j(x) - c_j^T Q_j c_j, 1e-10)
+ *   y_sj(x) = mu_j(x) + c_j(x)^T G_sj + sqrt(v_j(x)) W[s, j]                            W (S, m): the resident Monte-Carlo samples, S <= 256
+ *   T_ls = max(best_l, max_i U(theta_l, F_s[:, i]))                                     best_l: the best-so-far of the Monte-Carlo acquisitions
+ *   alpha(x | P) = (1/Ha) sum_h sum_l p_l (1/S) sum_s max(U(theta_l, y_s(x)) - T_ls, 0)
+ * (F, G, c, y) is the Cholesky factor of the bordered joint covariance of [f(P), f(x)], so alpha(x | P) = qEI(P u {x}) - qEI(P) for the same
+ * normals.  The latent, noiseless variance is used on purpose.  fp64 only, local to the context, state left as for the look-ahead entry
+ * points above (the resident reference set included); every failure returns < 0 with the entry point's name in the error text.
+ *
+ * bocf_set_pending_points: stages P = Xp (r, d) for all M outputs in buffers of its own (as the reference set is staged), forms
+ *   Sigma_j(P, P), factorizes it on the host with at most max_jitter_tries rungs and uploads Q, F, G.  Needs resident Monte-Carlo samples
+ *   with S equal to theirs.  jitter_out (M) or NULL receives tau.  Returns 0, or j + 1 for the first output that stays indefinite.  The
+ *   pending set stays resident until it is replaced; it is dropped by whatever drops the reference set.
+ * bocf_get_pending_samples: F_out (M, r, S) = the joint samples F at the pending points, as the device holds them.
+ * bocf_acq_pending: alpha(x | P) of every resident candidate into acq_out (C) or NULL (the values stay in the acquisition vector for the
+ *   top-k selection); dacq_out (C, d) or NULL: d alpha / dx with P, Zp, W fixed --
+ *   dy_sj/dx = dmu_j/dx + G_sj^T dc_j/dx + W[s, j] dv_j/dx / (2 sqrt(v_j)),  dv_j/dx = dsigma^2_j/dx - 2 (Q_j c_j)^T dc_j/dx (zero where the
+ *   clip is active).  theta (L, theta_dim), prob (L) or NULL (= 1 / L); BOCF_UTIL_PROGRAM is refused.  With option hyper_samples = H the
+ *   first acq_hyper_samples are averaged.  The candidates are worked off in chunks whose V fits in "workspace_mb"; the gradient form holds
+ *   d Sigma / dx of every (output, candidate, pending point) at once, in one chunk. */
+int bocf_set_pending_points(bocf_ctx* ctx, const double* Xp, int r, const double* Zp, int S, int max_jitter_tries, double* jitter_out);
+int bocf_get_pending_samples(bocf_ctx* ctx, double* F_out);
+int bocf_acq_pending(bocf_ctx* ctx, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim,
+                     const double* prob, int L, double* acq_out, double* dacq_out);
+
 /* ---- multi-GPU: candidate shards, ONE collective.  One process per GPU, one context per process.  The
  * reference's own candidate parallelism is a pathos process pool over single candidates (uEI_noiseless.py:85-97); here rank
  * r scores the contiguous slice [lo_r, hi_r) of the batch against its resident fit and the ranks exchange only their k
