@@ -69,12 +69,23 @@ static int check_fit_input(bocf_ctx* c, const char* who, const FitInput& in) {
   return 0;
 }
 
-// A new resident model of in's shape: the previous fit and everything derived from it are gone, the pending kernel ids are taken.
-static int begin_model(bocf_ctx* c, const FitInput& in) {
-  c->fitted = false; c->canned = false; c->sharded = false; c->have_acq = false; c->r32_valid = false; c->ri8_valid = false;
+// The factor R changes (a new model, an appended observation): every copy and product made FROM R is stale -- the fp32 and int8 copies
+// of the predict pass, the Ky^-1 = R R^T an inference's schedule left in the T scratch -- and so is what was staged or scored with the
+// old posterior: the acquisition vector, the Thompson samples, the reference set (uKG) and the pending points.  THE one place: a new
+// derived copy of R is dropped here, and both bocf_append and every new model go through it.
+static void factor_changed(bocf_ctx* c) {
+  c->r32_valid = false; c->ri8_valid = false;
+  c->kinv_done = 0;
+  c->have_acq = false;
   bocf_thompson_drop(c);
   bocf_kg_drop(c);
   bocf_pending_drop(c);
+}
+
+// A new resident model of in's shape: the previous fit and everything derived from it are gone, the pending kernel ids are taken.
+static int begin_model(bocf_ctx* c, const FitInput& in) {
+  c->fitted = false; c->canned = false; c->sharded = false;
+  factor_changed(c);
   c->N = in.N; c->Np = round_up(in.N, BOCF_TILE); c->d = in.d; c->m = in.m; c->kernel_id = in.kernel_id;
   c->xs_stride = (long)c->Np * in.d;
   return take_kernel_ids(c, in.m);
@@ -580,6 +591,12 @@ extern "C" int bocf_update_targets(bocf_ctx* c, const double* Y, double* lml_out
   return refresh_targets(c, Y, lml_out);
 }
 
+// One more observation by the bordered factor (fit.hip, append_write_kernel) instead of a refit.  Returns 1 -- the caller refits -- when it
+// cannot: no padding row left (N = Np), an output carries jitter, the fit is output-sharded, or the new pivot is inside the rounding noise
+// (then the context is un-fitted: some outputs may already be extended).  Everything derived from the N-point factor is dropped
+// (factor_changed); new targets alone (bocf_update_targets) keep the copies of R and Ky^-1, which do not depend on Y.
+// Covered by tests/test_gpu_incremental.py: tile and grid boundaries, every schedule's padding, reused buffers, the derived copies, a
+// chain of 127 appends against the long-double truth, each refusal.
 extern "C" int bocf_append(bocf_ctx* c, const double* x_new, const double* Y, double* lml_out) {
   if (!c || !c->fitted || c->canned || !x_new || !Y) return fail("bocf_append", "model not fitted / null argument");
   if (c->sharded) return 1;                              // an output-sharded fit keeps no upper factor to border: the caller refits
@@ -589,15 +606,14 @@ extern "C" int bocf_append(bocf_ctx* c, const double* x_new, const double* Y, do
   for (int j = 0; j < m; ++j)
     if (c->jitter[j] != 0.0) return 1;                 // a jittered factor is not extended (the ladder decides from scratch)
   const long strideS = (long)Np * Np, strideE = (long)nb * BOCF_TILE * BOCF_TILE;
-  c->have_acq = false;
+  // from here on R is being rewritten (and the predict pass's workspaces reused): nothing derived from the N-point factor is served again,
+  // whether the pivot below holds (the N + 1-point model) or not (un-fitted)
+  factor_changed(c);
   if (c->Xc.ensure(sizeof(double) * d) || c->Kstar.ensure(sizeof(double) * (size_t)m * Np * BOCF_TILE) ||
       c->sumsq.ensure(sizeof(double) * (size_t)m * BOCF_TILE) || c->Vs.ensure(sizeof(double) * (size_t)m * Np * BOCF_SMALL_N) ||
       c->Ws.ensure(sizeof(double) * (size_t)m * Np * BOCF_SMALL_N) || c->meanpart.ensure(sizeof(double) * (size_t)2 * m * nb * Np))
     return -1;
   c->C = 0;                                            // the resident candidate batch is replaced
-  bocf_thompson_drop(c);
-  bocf_kg_drop(c);
-  bocf_pending_drop(c);
   HIPCHK(hipMemcpyAsync(c->Xc.p, x_new, sizeof(double) * d, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemsetAsync(c->info.p, 0, sizeof(int) * m, c->stream));
   // k(X, x_new) as column 0 of a 128-wide K* block, u = R^T k, ||u||^2, w = R u
@@ -623,7 +639,6 @@ extern "C" int bocf_append(bocf_ctx* c, const double* x_new, const double* Y, do
   launch_scale_inputs(c->X.as<double>() + (size_t)N * d, 1, d, c->hypd.as<KernHyp>(), m, c->Xs.as<double>() + (size_t)N * d, c->xs_stride,
                       c->stream);
   c->N = N + 1;
-  c->r32_valid = false; c->ri8_valid = false;
   if (c->mu_train.ensure(sizeof(double) * (size_t)m * c->N)) return -1;
   return refresh_targets(c, Y, lml_out);
 }

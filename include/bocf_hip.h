@@ -175,8 +175,10 @@ int bocf_update_targets(bocf_ctx* ctx, const double* Y, double* lml_out);
 /* Rank-1 append of ONE observation x_new (d) with the complete new targets Y (m,N+1): borders the resident
  * factor U and its inverse R in O(N^2) instead of refitting in O(N^3) (the reference refits: cbo.py:363,419 ->
  * GP.set_XY).  Returns 0 on success; 1 when the caller must run bocf_fit instead (padding exhausted, i.e. N is
- * a multiple of 128; a jittered factor; or a non-positive new pivot, in which case the context is marked
- * unfitted). */
+ * a multiple of 128; a jittered factor; an output-sharded fit; or a non-positive new pivot, in which case the
+ * context is marked unfitted).  On success everything derived from the old factor is dropped: the candidate
+ * batch and its acquisition vector, the reference / pending / Thompson sets, the reduced-precision copies of R
+ * and the inverse of Ky an inference left for bocf_lml_gradients (which is then formed anew). */
 int bocf_append(bocf_ctx* ctx, const double* x_new, const double* Y, double* lml_out);
 
 /* Gradients of the log marginal likelihood of the CURRENT fit w.r.t. the raw hyper-parameters: kernel variance

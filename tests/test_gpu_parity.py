@@ -594,7 +594,9 @@ def test_hyper_gradients_multi_tile(B):
         np.testing.assert_allclose(dn[j], rn, rtol=1e-6)
 
 
-# incremental updateModel: targets-only refresh and rank-1 append equal a from-scratch fit
+# incremental updateModel: targets-only refresh and rank-1 append equal a from-scratch fit (N = 120 .. 135, one padding
+# boundary).  The other tile / grid boundaries, schedules, reused buffers, derived copies of R, long chains and the refusals:
+# tests/test_gpu_incremental.py
 def test_incremental_update(B):
     d, m, C = 4, 3, 200
     p = R.synthetic_problem(140, d, m, C, 8, 909, noise=1e-4)
