@@ -114,6 +114,39 @@ SIGNATURES = {
     "bocf_option_check": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_longlong]),
 }
 
+
+def _desc(name, fields):
+    return type(name, (ctypes.Structure,), {"_fields_": fields})
+
+
+_L, _D, _I = ctypes.c_long, ctypes.c_double, ctypes.c_int
+_c_int_p = ctypes.POINTER(ctypes.c_int)
+# descriptors of the probes-only launcher entries (csrc/capi_probe.hip), field for field
+ProbeGemmF64 = _desc("ProbeGemmF64", [
+    ("A", _c_double_p), ("lenA", _L), ("offA", _L), ("B", _c_double_p), ("lenB", _L), ("offB", _L), ("C", _c_double_p), ("lenC", _L), ("offC", _L),
+    ("sumsq", _c_double_p), ("lenS", _L), ("offS", _L), ("lda", _L), ("strideA", _L), ("strideA2", _L), ("ldb", _L), ("strideB", _L), ("strideB2", _L),
+    ("ldc", _L), ("strideC", _L), ("strideC2", _L), ("strideSumsq", _L), ("alpha", _D), ("beta", _D)] + [(f, _I) for f in (
+        "M", "Ncols", "K", "kb", "krt", "kct", "kbeg_rt", "kbeg_ct", "batch1", "upper_only", "rt_desc", "ct_desc", "swizzle", "prefetch1", "stagger", "no_x3",
+        "vprobe", "batch", "epilogue", "has_cin", "b_alias_c", "use_queue", "ncu", "repeat")] + [("ctr", _I * 2)])
+ProbeGemmF32 = _desc("ProbeGemmF32", [
+    ("A", _c_double_p), ("lenA", _L), ("offA", _L), ("B", _c_double_p), ("lenB", _L), ("offB", _L), ("sumsq", _c_double_p), ("lenS", _L), ("offS", _L),
+    ("lda", _L), ("strideA", _L), ("ldb", _L), ("strideB", _L), ("strideSumsq", _L)] + [(f, _I) for f in ("M", "Ncols", "K", "tile128", "batch", "repeat")])
+ProbeVarI8 = _desc("ProbeVarI8", [
+    ("A", _c_double_p), ("lenA", _L), ("B", _c_double_p), ("lenB", _L), ("offB", _L), ("sumsq", _c_double_p), ("lenS", _L), ("offS", _L),
+    ("eA", _c_int_p), ("eB", _c_int_p), ("strideA", _L), ("ldb", _L), ("strideB", _L), ("strideSumsq", _L)] + [(f, _I) for f in (
+        "Np", "ncols", "m", "i8_group", "repeat")])
+ProbeTile128 = _desc("ProbeTile128", [
+    ("A", _c_double_p), ("lenA", _L), ("offA", _L), ("B", _c_double_p), ("lenB", _L), ("offB", _L), ("C", _c_double_p), ("lenC", _L), ("offC", _L),
+    ("lda", _L), ("strideA", _L), ("ldb", _L), ("strideB", _L), ("ldc", _L), ("strideC", _L), ("alpha", _D), ("beta", _D)] + [(f, _I) for f in (
+        "ntiles", "K", "m", "b_alias_c", "repeat")])
+# symbols that exist in libbocf_hip_probes.so ONLY (not in include/bocf_hip.h, not exported by the product library)
+PROBE_SIGNATURES = {
+    "bocf_probe_gemm_f64": (ctypes.c_int, [ctypes.POINTER(ProbeGemmF64)]),
+    "bocf_probe_gemm_f32": (ctypes.c_int, [ctypes.POINTER(ProbeGemmF32)]),
+    "bocf_probe_var_i8": (ctypes.c_int, [ctypes.POINTER(ProbeVarI8)]),
+    "bocf_probe_tile128": (ctypes.c_int, [ctypes.POINTER(ProbeTile128)]),
+}
+
 _libs = {}
 _current = "probes" if os.environ.get("BOCF_PROBES") == "1" else "product"
 
@@ -130,7 +163,7 @@ def _load(which):
         raise ImportError("%s not found at %s -- build it with `python -m bocf_amd.build%s` "
                           "(there is no CPU fallback)" % (os.path.basename(path), path, "" if which == "product" else " --probes"))
     lib = ctypes.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + (list(PROBE_SIGNATURES.items()) if which == "probes" else []):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

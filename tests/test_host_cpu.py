@@ -19,6 +19,21 @@ def test_library_exports_every_declared_symbol():
         assert getattr(lib, name) is not None, name
     assert declared == set(bocf_amd._ffi.SIGNATURES), declared ^ set(bocf_amd._ffi.SIGNATURES)
     assert lib.bocf_version() >= 100
+    # the launcher probes (csrc/capi_probe.hip) exist in the probes build only: the product exports none of them, the probes build all,
+    # the header declares none, and the binding knows exactly the entries the source defines
+    probe_src = open(os.path.join(ROOT, "bocf_amd", "csrc", "capi_probe.hip")).read()
+    defined = set(re.findall(r"^int (bocf_probe_[a-z0-9_]+)\(", probe_src, re.M))
+    assert len(defined) == 4 and defined == set(bocf_amd._ffi.PROBE_SIGNATURES), defined ^ set(bocf_amd._ffi.PROBE_SIGNATURES)
+    assert not defined & declared and not defined & set(bocf_amd._ffi.SIGNATURES)
+    for name in defined:
+        assert not hasattr(lib, name), name
+    with open(bocf_amd._ffi.LIB_PATH, "rb") as f:
+        assert b"bocf_probe_" not in f.read()
+    with bocf_amd._ffi.probes_library() as plib:
+        for name in defined:
+            assert getattr(plib, name) is not None, name
+        for name in declared:
+            assert getattr(plib, name) is not None, name
 
 
 def test_option_table_of_the_product_has_no_probe_and_validates_ranges():
