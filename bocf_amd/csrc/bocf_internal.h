@@ -2,10 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "kern_dispatch.h"     // BOCF_MAX_D (max input dimension), bocf_dispatch_d, bocf_dispatch_family, bocf_family_runs
 
 #define BOCF_TILE 128          // panel width NB == GEMM tile edge; every matrix is padded to it
-#define BOCF_MAX_D 32          // max input dimension
-#define BOCF_MAX_M 16          // max model outputs (per hyper-sample)
+#define BOCF_MAX_M 16         // max model outputs (per hyper-sample)
 #define BOCF_MAX_FITS 1024     // max independent factorizations in one fit (hyper-samples x outputs)
 #define BOCF_MAX_L 32          // max utility-parameter support size on device
 
@@ -18,6 +18,11 @@ void bocf_note_launch(const char* kernel, hipError_t e);
     hipLaunchKernelGGL(kern, grid, block, shm, stream, __VA_ARGS__);  \
     bocf_note_launch(#kern, hipGetLastError());                       \
   } while (0)
+// bocf_dispatch_d behind a launcher: an input dimension that no instantiation covers is reported as a failed launch of `kernel`
+template <typename F>
+static inline void bocf_launch_by_d(const char* kernel, int d, F f) {
+  if (!bocf_dispatch_d(d, f)) bocf_note_launch(kernel, hipErrorInvalidValue);
+}
 
 // s + c += a * b with the running sum carried as an unevaluated pair (s, c): TwoProd through fma, TwoSum (Knuth).  The posterior
 // mean sum_k K(x*, X_k) alpha_k is a sum of N terms of size |alpha| ~ 1e6 (cond(Ky) ~ 4e9 at BASELINE configs[2]) that cancels to O(1):
@@ -61,24 +66,6 @@ __device__ __forceinline__ double bocf_exp_nonpos(double x) {
   p = __builtin_fma(t, p, 1.0);
   p = __builtin_fma(t, p, 1.0);
   return __builtin_ldexp(p, (int)dn);
-}
-
-// Outputs may use different kernel FAMILIES (the reference's multi_outputGP takes a kernel list, multi_outputGP.py:44-47).  The kernels
-// that evaluate a covariance function are specialised per family at compile time, so a launcher that is given `kids` (host array of m
-// kernel ids, or nullptr = every output uses `kernel_id`) issues one launch per RUN of equal ids, with its pointers advanced to the
-// run's first output: f(j0, m_run, kernel_id_of_the_run).
-template <typename F>
-static inline void bocf_family_runs(int kernel_id, const int* kids, int m, F f) {
-  if (!kids) {
-    f(0, m, kernel_id);
-    return;
-  }
-  for (int j0 = 0; j0 < m;) {
-    int j1 = j0 + 1;
-    while (j1 < m && kids[j1] == kids[j0]) ++j1;
-    f(j0, j1 - j0, kids[j0]);
-    j0 = j1;
-  }
 }
 
 // ---------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@
 // GPy/util/linalg.py:52-55), R = U^-1 upper.  Padding rows/cols carry the identity.
 #include "bocf_internal.h"
 #include "fit_device.h"
+#include "kern_family.h"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -126,33 +127,19 @@ __global__ __launch_bounds__(256) void build_train_lds_kernel(const double* __re
 
 void launch_build_train_kernel(const double* Xs, long strideXs, int N, int Np, int d, int kernel_id, const KernHyp* hyp,
                                const double* jitter, int add_diag, double* S, long strideS, int m, hipStream_t s, const int* kids) {
-  if (kids) {
-    bocf_family_runs(kernel_id, kids, m, [&](int j0, int mr, int kid_) {
-      launch_build_train_kernel(Xs + (long)j0 * strideXs, strideXs, N, Np, d, kid_, hyp + j0, jitter ? jitter + j0 : nullptr, add_diag, S + (long)j0 * strideS,
-                                strideS, mr, s, nullptr);
-    });
-    return;
-  }
   // tiles on / above the diagonal: row block rb (BT_ROWS rows) holds the 512-column blocks from rb * BT_ROWS / 512 on
   unsigned ntiles = 0;
   for (int rb = 0; rb < Np / BT_ROWS; ++rb) ntiles += (unsigned)((Np + 511) / 512 - rb * BT_ROWS / 512);
-  dim3 grid(ntiles, 1, (unsigned)m);
-  const int kid = kernel_id <= 1 ? 0 : kernel_id;
-#define LAUNCH(D, KID) BOCF_LAUNCH((build_train_lds_kernel<D, KID>), grid, dim3(256), 0, s, Xs, strideXs, N, Np, hyp, jitter, add_diag, S, strideS)
-#define CASE(D)                       \
-  case D:                             \
-    if (kid == 0) LAUNCH(D, 0);       \
-    else if (kid == 2) LAUNCH(D, 2);  \
-    else LAUNCH(D, 3);                \
-    break;
-  switch (d) {
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15)
-    CASE(16) CASE(17) CASE(18) CASE(19) CASE(20) CASE(21) CASE(22) CASE(23) CASE(24) CASE(25) CASE(26) CASE(27) CASE(28) CASE(29)
-    CASE(30) CASE(31) CASE(32)
-    default: break;
-  }
-#undef CASE
-#undef LAUNCH
+  bocf_family_runs(kernel_id, kids, m, [&](int j0, int mr, int kid) {
+    const dim3 grid(ntiles, 1, (unsigned)mr);
+    bocf_launch_by_d("build_train_lds_kernel", d, [&](auto Dc) {
+      bocf_dispatch_family(kid, [&](auto Kc) {
+        constexpr int D = decltype(Dc)::value, KID = decltype(Kc)::value;
+        BOCF_LAUNCH((build_train_lds_kernel<D, KID>), grid, dim3(256), 0, s, Xs + (long)j0 * strideXs, strideXs, N, Np, hyp + j0,
+                    jitter ? jitter + j0 : nullptr, add_diag, S + (long)j0 * strideS, strideS);
+      });
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -234,30 +221,16 @@ int kalpha_block(int Np) { return Np >= 4096 ? NB : (Np >= 2048 ? 64 : 32); }
 void launch_kalpha_dd(const double* Xs, long strideXs, int N, int Np, int d, int kernel_id, const KernHyp* hyp, const double* jitter,
                       const double* alpha, double* part, int m, hipStream_t s, const int* kids) {
   const int kb = kalpha_block(Np);
-  if (kids) {
-    bocf_family_runs(kernel_id, kids, m, [&](int j0, int mr, int kid_) {
-      launch_kalpha_dd(Xs + (long)j0 * strideXs, strideXs, N, Np, d, kid_, hyp + j0, jitter ? jitter + j0 : nullptr, alpha + (long)j0 * Np,
-                       part + (long)j0 * (Np / kb) * 2 * Np, mr, s, nullptr);
+  bocf_family_runs(kernel_id, kids, m, [&](int j0, int mr, int kid) {
+    const dim3 grid((unsigned)((Np + 255) / 256), (unsigned)(Np / kb), (unsigned)mr);
+    bocf_launch_by_d("kalpha_dd_kernel", d, [&](auto Dc) {
+      bocf_dispatch_family(kid, [&](auto Kc) {
+        constexpr int D = decltype(Dc)::value, KID = decltype(Kc)::value;
+        BOCF_LAUNCH((kalpha_dd_kernel<D, KID>), grid, dim3(256), 0, s, Xs + (long)j0 * strideXs, strideXs, N, Np, hyp + j0,
+                    jitter ? jitter + j0 : nullptr, alpha + (long)j0 * Np, part + (long)j0 * (Np / kb) * 2 * Np, kb);
+      });
     });
-    return;
-  }
-  dim3 grid((unsigned)((Np + 255) / 256), (unsigned)(Np / kb), (unsigned)m);
-  const int kid = kernel_id <= 1 ? 0 : kernel_id;
-#define LAUNCH(D, KID) BOCF_LAUNCH((kalpha_dd_kernel<D, KID>), grid, dim3(256), 0, s, Xs, strideXs, N, Np, hyp, jitter, alpha, part, kb)
-#define CASE(D)                       \
-  case D:                             \
-    if (kid == 0) LAUNCH(D, 0);       \
-    else if (kid == 2) LAUNCH(D, 2);  \
-    else LAUNCH(D, 3);                \
-    break;
-  switch (d) {
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15)
-    CASE(16) CASE(17) CASE(18) CASE(19) CASE(20) CASE(21) CASE(22) CASE(23) CASE(24) CASE(25) CASE(26) CASE(27) CASE(28) CASE(29)
-    CASE(30) CASE(31) CASE(32)
-    default: break;
-  }
-#undef CASE
-#undef LAUNCH
+  });
 }
 
 __global__ void refine_rhs_kernel(const double* __restrict__ part, int N, int Np, const double* __restrict__ yc, double* __restrict__ r, int nblk) {
@@ -379,19 +352,9 @@ void launch_lml(const double* S, long strideS, int N, int Np, const double* alph
 //   d/dnoise    = sum_i dL_dK_ii                                :63, gaussian.py:71-72
 //   d/dvariance = sum_ij dL_dK_ij K_ij / variance               stationary.py:197, se.py:181
 //   d/dl_q      = sum_ij dL_dK_ij f_ij (x_iq - x_jq)^2 / l_q^3  stationary.py:203-212,236-237, se.py:183
-// with f = -invdist dK_dr (RBF/SE: k;  Matern52: (5/3) s2 (1 + sqrt5 r) e^{-sqrt5 r};  Matern32: 3 s2 e^{-sqrt3 r}).
+// with f = -invdist dK_dr (kern_family.h: kern_f_amp times the exponential the kernel value takes).
 // Ky^-1 = R R^T comes from a triangular GEMM (upper tiles); every (i<j) pair is visited once and counted twice.
 // One 64 x 256 tile per workgroup, thread per column; per-workgroup partials are reduced in a fixed order.
-__device__ __forceinline__ double kern_hfac(int kid, double variance, double r2) {
-  if (kid <= 1) return variance * bocf_exp_nonpos(-0.5 * r2);
-  const double r = sqrt(r2);
-  if (kid == 2) {
-    const double s5r = 2.23606797749978969641 * r;
-    return (5.0 / 3.0) * variance * (1.0 + s5r) * bocf_exp_nonpos(-s5r);
-  }
-  return 3.0 * variance * bocf_exp_nonpos(-1.73205080756887729353 * r);
-}
-
 // rows per workgroup: 16 up to 1024 points (a thread walks its rows one dependent exp after the other: 64 rows are 34 us at N = 256 whatever the
 // size of the grid), 64 above
 static inline int hypgrad_rows(int Np) { return Np <= 1024 ? 16 : 64; }
@@ -434,22 +397,8 @@ __global__ __launch_bounds__(256) void hypgrad_kernel(const double* __restrict__
           df[q] = X[(long)gr * D + q] - xc[q];
           r2 += df[q] * df[q];
         }
-        double kv, f;
-        if (KID <= 1) {
-          kv = variance * bocf_exp_nonpos(-0.5 * r2);
-          f = kv;
-        } else {
-          const double r = sqrt(r2);
-          if (KID == 2) {
-            const double s5r = 2.23606797749978969641 * r, e = bocf_exp_nonpos(-s5r);
-            kv = variance * (1.0 + s5r + (5.0 / 3.0) * r2) * e;
-            f = (5.0 / 3.0) * variance * (1.0 + s5r) * e;
-          } else {
-            const double s3r = 1.73205080756887729353 * r, e = bocf_exp_nonpos(-s3r);
-            kv = variance * (1.0 + s3r) * e;
-            f = 3.0 * variance * e;
-          }
-        }
+        const double u = kern_decay<KID>(r2), e = bocf_exp_nonpos(-u);
+        const double kv = kern_value_amp<KID>(variance, r2, u) * e, f = kern_f_amp<KID>(variance, u) * e;
         const double g2 = 2.0 * g;                       // (i,j) and (j,i)
         sv += g2 * kv / variance;
         const double gf = g2 * f;
@@ -492,32 +441,19 @@ __global__ __launch_bounds__(64) void hypgrad_reduce_kernel(const double* __rest
 
 void launch_hypgrad(const double* Xs, long strideXs, int N, int Np, int d, int kernel_id, const KernHyp* hyp, const double* alpha,
                     const double* Kinv, long strideK, double* part, double* out, int m, hipStream_t s, const int* kids, bool reduce) {
-  if (kids) {
-    bocf_family_runs(kernel_id, kids, m, [&](int j0, int mr, int kid_) {
-      launch_hypgrad(Xs + (long)j0 * strideXs, strideXs, N, Np, d, kid_, hyp + j0, alpha + (long)j0 * Np, Kinv + (long)j0 * strideK, strideK,
-                     part + (long)j0 * hypgrad_num_blocks(Np) * (2 + d), out + (long)j0 * (2 + d), mr, s, nullptr, reduce);
+  const int rows = hypgrad_rows(Np), nblk = hypgrad_num_blocks(Np);
+  bocf_family_runs(kernel_id, kids, m, [&](int j0, int mr, int kid) {
+    const dim3 grid((unsigned)((Np + 255) / 256), (unsigned)(Np / rows), (unsigned)mr);
+    double* pt = part + (long)j0 * nblk * (2 + d);
+    bocf_launch_by_d("hypgrad_kernel", d, [&](auto Dc) {
+      bocf_dispatch_family(kid, [&](auto Kc) {
+        constexpr int D = decltype(Dc)::value, KID = decltype(Kc)::value;
+        BOCF_LAUNCH((hypgrad_kernel<D, KID>), grid, dim3(256), 0, s, Xs + (long)j0 * strideXs, strideXs, N, Np, hyp + j0, alpha + (long)j0 * Np,
+                    Kinv + (long)j0 * strideK, strideK, pt, rows);
+      });
     });
-    return;
-  }
-  const int rows = hypgrad_rows(Np);
-  dim3 grid((unsigned)((Np + 255) / 256), (unsigned)(Np / rows), (unsigned)m);
-  const int kid = kernel_id <= 1 ? 0 : kernel_id;
-#define LAUNCH(D, KID) BOCF_LAUNCH((hypgrad_kernel<D, KID>), grid, dim3(256), 0, s, Xs, strideXs, N, Np, hyp, alpha, Kinv, strideK, part, rows)
-#define CASE(D)                       \
-  case D:                             \
-    if (kid == 0) LAUNCH(D, 0);       \
-    else if (kid == 2) LAUNCH(D, 2);  \
-    else LAUNCH(D, 3);                \
-    break;
-  switch (d) {
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15)
-    CASE(16) CASE(17) CASE(18) CASE(19) CASE(20) CASE(21) CASE(22) CASE(23) CASE(24) CASE(25) CASE(26) CASE(27) CASE(28) CASE(29)
-    CASE(30) CASE(31) CASE(32)
-    default: break;
-  }
-#undef CASE
-#undef LAUNCH
-  if (reduce) BOCF_LAUNCH(hypgrad_reduce_kernel, dim3((unsigned)m), dim3(64), 0, s, part, hypgrad_num_blocks(Np), d, hyp, out);
+    if (reduce) BOCF_LAUNCH(hypgrad_reduce_kernel, dim3((unsigned)mr), dim3(64), 0, s, pt, nblk, d, hyp + j0, out + (long)j0 * (2 + d));
+  });
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 // built on it (exact_gaussian_inference.py:46-63, stationary.py:191-214; GPy/inference/mcmc/hmc.py:30-69).
 #include "bocf_internal.h"
 #include "fit_device.h"
+#include "kern_family.h"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -81,21 +82,9 @@ __device__ __forceinline__ void infer128_body(const double* __restrict__ X, int 
                 r2 += df * df;
               }
               // (kern_of_r2 with the exponential kept)
-              if (KID <= 1) {
-                e = bocf_exp_nonpos(-0.5 * r2);
-                v = variance * e;
-              } else {
-                const double rr = sqrt(r2);
-                if (KID == 2) {
-                  const double s5r = 2.23606797749978969641 * rr;
-                  e = bocf_exp_nonpos(-s5r);
-                  v = variance * (1.0 + s5r + (5.0 / 3.0) * r2) * e;
-                } else {
-                  const double s3r = 1.73205080756887729353 * rr;
-                  e = bocf_exp_nonpos(-s3r);
-                  v = variance * (1.0 + s3r) * e;
-                }
-              }
+              const double u = kern_decay<KID>(r2);
+              e = bocf_exp_nonpos(-u);
+              v = kern_value_amp<KID>(variance, r2, u) * e;
               if (row == col) v = variance + dg;
             } else {
               v = (row == col) ? 1.0 : 0.0;
@@ -284,27 +273,14 @@ __device__ __forceinline__ void infer128_body(const double* __restrict__ X, int 
               sv += g;                                     // K_ii / variance = 1
             } else {
               const double e = ex[jj][A][r];
-              double kv, f;
-              if (KID <= 1) {
-                kv = variance * e;
-                f = kv;
-              } else {
-                double r2 = 0.0;
+              double r2 = 0.0;                             // (family 0 is made of e alone: no second pass over the coordinates)
+              if (kern_uses_r<KID>)
                 for (int q = 0; q < d; ++q) {
                   const double df = xs[row * d + q] - xs[col * d + q];
                   r2 += df * df;
                 }
-                const double rr = sqrt(r2);
-                if (KID == 2) {
-                  const double s5r = 2.23606797749978969641 * rr;
-                  kv = variance * (1.0 + s5r + (5.0 / 3.0) * r2) * e;
-                  f = (5.0 / 3.0) * variance * (1.0 + s5r) * e;
-                } else {
-                  const double s3r = 1.73205080756887729353 * rr;
-                  kv = variance * (1.0 + s3r) * e;
-                  f = 3.0 * variance * e;
-                }
-              }
+              const double u = kern_decay<KID>(r2);
+              const double kv = kern_value_amp<KID>(variance, r2, u) * e, f = kern_f_amp<KID>(variance, u) * e;
               const double g2 = 2.0 * g;
               sv += g2 * kv / variance;
               w2 = g2 * f;
@@ -630,29 +606,23 @@ __global__ __launch_bounds__(256, 1) void hmc128_kernel(HmcArgs a) {
 }
 
 void launch_hmc128(const HmcArgs& a, int kernel_id, int m, hipStream_t s, const int* kids) {
-  if (kids) {
-    bocf_family_runs(kernel_id, kids, m, [&](int j0, int mr, int kid_) {
-      HmcArgs r = a;                                       // the run's slice of every per-output array
-      r.yc = a.yc + (long)j0 * NB;
-      r.theta = a.theta + (long)j0 * a.P;
-      r.fixed = a.fixed + (long)j0 * a.P;
-      r.mom = a.mom + (long)j0 * a.ns * a.P;
-      r.uni = a.uni + (long)j0 * a.ns;
-      r.chains = a.chains + (long)j0 * a.ns * a.P;
-      r.accepted = a.accepted + j0;
-      r.diverged = a.diverged + j0;
-      r.status = a.status + j0;
-      r.n_infer = a.n_infer + j0;
-      launch_hmc128(r, kid_, mr, s, nullptr);
+  bocf_family_runs(kernel_id, kids, m, [&](int j0, int mr, int kid) {
+    HmcArgs r = a;                                         // the run's slice of every per-output array
+    r.yc = a.yc + (long)j0 * NB;
+    r.theta = a.theta + (long)j0 * a.P;
+    r.fixed = a.fixed + (long)j0 * a.P;
+    r.mom = a.mom + (long)j0 * a.ns * a.P;
+    r.uni = a.uni + (long)j0 * a.ns;
+    r.chains = a.chains + (long)j0 * a.ns * a.P;
+    r.accepted = a.accepted + j0;
+    r.diverged = a.diverged + j0;
+    r.status = a.status + j0;
+    r.n_infer = a.n_infer + j0;
+    bocf_dispatch_family(kid, [&](auto Kc) {
+      constexpr int KID = decltype(Kc)::value;
+      BOCF_LAUNCH((hmc128_kernel<KID, 1>), dim3((unsigned)mr), dim3(256), 0, s, r);
     });
-    return;
-  }
-  const int kid = kernel_id <= 1 ? 0 : kernel_id;
-#define LAUNCH(KID) BOCF_LAUNCH((hmc128_kernel<KID, 1>), dim3((unsigned)m), dim3(256), 0, s, a)
-  if (kid == 0) LAUNCH(0);
-  else if (kid == 2) LAUNCH(2);
-  else LAUNCH(3);
-#undef LAUNCH
+  });
 #ifdef BOCF_PROBES
   if (getenv("BOCF_DBG_ITS")) {
     unsigned long long h[8];
@@ -667,18 +637,12 @@ void launch_hmc128(const HmcArgs& a, int kernel_id, int m, hipStream_t s, const 
 
 void launch_infer128(const double* X, int N, int d, int kernel_id, const KernHyp* hyp, const double* yc, double* out, int m, hipStream_t s,
                      const int* kids) {
-  if (kids) {
-    bocf_family_runs(kernel_id, kids, m, [&](int j0, int mr, int kid_) {
-      launch_infer128(X, N, d, kid_, hyp + j0, yc + (long)j0 * NB, out + (long)j0 * (2 + d + 2), mr, s, nullptr);
+  bocf_family_runs(kernel_id, kids, m, [&](int j0, int mr, int kid) {
+    bocf_dispatch_family(kid, [&](auto Kc) {
+      constexpr int KID = decltype(Kc)::value;
+      BOCF_LAUNCH((infer128_kernel<KID, 1>), dim3((unsigned)mr), dim3(256), 0, s, X, N, d, hyp + j0, yc + (long)j0 * NB, out + (long)j0 * (2 + d + 2));
     });
-    return;
-  }
-  const int kid = kernel_id <= 1 ? 0 : kernel_id;
-#define LAUNCH(KID) BOCF_LAUNCH((infer128_kernel<KID, 1>), dim3((unsigned)m), dim3(256), 0, s, X, N, d, hyp, yc, out)
-  if (kid == 0) LAUNCH(0);
-  else if (kid == 2) LAUNCH(2);
-  else LAUNCH(3);
-#undef LAUNCH
+  });
 #ifdef BOCF_PROBES
   if (getenv("BOCF_DBG_ITS")) {
     static int shown = 0;
@@ -696,4 +660,3 @@ void launch_infer128(const double* X, int N, int d, int kernel_id, const KernHyp
   }
 #endif
 }
-

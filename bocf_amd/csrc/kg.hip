@@ -16,7 +16,7 @@
 // fp64 throughout.  Every sum and maximum has a fixed order; every kernel writes its own outputs only (no atomics).
 #include "bocf_internal.h"
 #include "../../include/bocf_hip.h"
-#include "kern_grad_dev.h"
+#include "kern_family.h"
 #include "utility_dev.h"
 #include "eu_dev.h"
 
@@ -44,7 +44,7 @@ void launch_kg_diag(const double* V, long ldv, long strideV, int K, int n, const
 }
 
 // ---------------------------------------------------------------------------------------------
-// One workgroup per (candidate, output).  g_i = f(r_i) (x_c - X_i) (scaled coordinates, kern_dfac of grad_kernel) of 64 training rows at a
+// One workgroup per (candidate, output).  g_i = f(r_i) (x_c - X_i) (scaled coordinates, kern_dfac of kern_family.h) of 64 training rows at a
 // time goes through LDS; thread t owns reference point a0 + t (+ 256, ...) and adds g_i Wa[i][a] over the rows in increasing order.
 #define CG_ROWS 64
 template <int D>
@@ -110,21 +110,11 @@ void launch_cov_grad(const double* Xs, long strideXs, int N, int d, int kernel_i
   if (m <= 0 || Cn <= 0 || an <= 0) return;
   bocf_family_runs(kernel_id, kids, m, [&](int j0, int mr, int kid) {
     const dim3 grid((unsigned)Cn, (unsigned)mr);
-    const double* xs = Xs + (long)j0 * strideXs;
-    const KernHyp* hy = hyp + j0;
-    const double* wa = Wa + (long)j0 * strideW;
-    double* o = out + (long)j0 * Cn * an * d;
-#define CASE(D)                                                                                                                     \
-  case D:                                                                                                                           \
-    BOCF_LAUNCH(cov_grad_kernel<D>, grid, dim3(256), 0, s, xs, strideXs, N, kid, hy, Xc, Cn, XA, a0, an, wa, ldw, strideW, o);      \
-    break;
-    switch (d) {
-      CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15)
-      CASE(16) CASE(17) CASE(18) CASE(19) CASE(20) CASE(21) CASE(22) CASE(23) CASE(24) CASE(25) CASE(26) CASE(27) CASE(28) CASE(29)
-      CASE(30) CASE(31) CASE(32)
-      default: break;
-    }
-#undef CASE
+    bocf_launch_by_d("cov_grad_kernel", d, [&](auto Dc) {
+      constexpr int D = decltype(Dc)::value;
+      BOCF_LAUNCH(cov_grad_kernel<D>, grid, dim3(256), 0, s, Xs + (long)j0 * strideXs, strideXs, N, kid, hyp + j0, Xc, Cn, XA, a0, an,
+                  Wa + (long)j0 * strideW, ldw, strideW, out + (long)j0 * Cn * an * d);
+    });
   });
 }
 

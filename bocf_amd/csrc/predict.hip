@@ -1,19 +1,8 @@
-// Predict-side kernels: cross kernel K* = K(X, X*) with the posterior mean fused in, and the
-// small finalisation kernels.  The N^2 C contraction itself is gemm_f64.hip.
+// Predict-side kernels: cross kernel K* = K(X, X*) with the posterior mean fused in, the small finalisation kernels, the input gradients
+// of the posterior and the small-batch path.  The N^2 C contraction itself is gemm_f64.hip, the covariance functions are kern_family.h.
 #include "bocf_internal.h"
 #include "../../include/bocf_hip.h"
-#include "kern_grad_dev.h"
-
-__device__ __forceinline__ double kern_of_r2_p(int kernel_id, double variance, double r2) {
-  if (kernel_id <= 1) return variance * bocf_exp_nonpos(-0.5 * r2);
-  const double r = sqrt(r2);
-  if (kernel_id == 2) {
-    const double s5r = 2.23606797749978969641 * r;
-    return variance * (1.0 + s5r + (5.0 / 3.0) * r2) * bocf_exp_nonpos(-s5r);
-  }
-  const double s3r = 1.73205080756887729353 * r;
-  return variance * (1.0 + s3r) * bocf_exp_nonpos(-s3r);
-}
+#include "kern_family.h"
 
 // One thread per PAIR of adjacent candidate columns, looping over a slice of the training points.  The training point is
 // wave-uniform (scalar loads), the two candidates' scaled coordinates live in registers, the store K*[kk][c..c+1] is one
@@ -24,7 +13,7 @@ typedef double v2d_p __attribute__((ext_vector_type(2)));
 typedef float v2f_p __attribute__((ext_vector_type(2)));
 template <int D, int KID, int STORE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D <= 8 ? 8 : 1)))
-void cross_kernel(const double* __restrict__ Xs, long strideXs, int N, int Np, int kernel_id_unused,
+void cross_kernel(const double* __restrict__ Xs, long strideXs, int N, int Np,
                                                     const KernHyp* __restrict__ hyp, const double* __restrict__ Xc, int c0, int Cn,
                                                     const double* __restrict__ alpha, double* __restrict__ Kstar, long ldk, long strideK,
                                                     double* __restrict__ meanpart, double* __restrict__ meanlo, int nsplit, int Cpad,
@@ -79,8 +68,8 @@ void cross_kernel(const double* __restrict__ Xs, long strideXs, int N, int Np, i
           r0 += d0 * d0;
           r1 += d1 * d1;
         }
-        const double v0 = kern_of_r2_p(KID, h.variance, r0);
-        const double v1 = kern_of_r2_p(KID, h.variance, r1);
+        const double v0 = kern_of_r2(KID, h.variance, r0);
+        const double v1 = kern_of_r2(KID, h.variance, r1);
         dd_fma_acc(mean0, lo0, v0, a);
         dd_fma_acc(mean1, lo1, v1, a);
         if (STORE == 1) __builtin_nontemporal_store((v2d_p){v0, v1}, reinterpret_cast<v2d_p*>(Kj + (long)kk * ldk + c));
@@ -118,8 +107,8 @@ void cross_kernel(const double* __restrict__ Xs, long strideXs, int N, int Np, i
             r0 += d0 * d0;
             r1 += d1 * d1;
           }
-          v0 = kern_of_r2_p(KID, h.variance, r0);
-          v1 = kern_of_r2_p(KID, h.variance, r1);
+          v0 = kern_of_r2(KID, h.variance, r0);
+          v1 = kern_of_r2(KID, h.variance, r1);
           const double a = al[kk];
           dd_fma_acc(mean0, lo0, v0, a);
           dd_fma_acc(mean1, lo1, v1, a);
@@ -135,63 +124,26 @@ void cross_kernel(const double* __restrict__ Xs, long strideXs, int N, int Np, i
   }
 }
 
-template <int D>
-static void launch_cross_d(const double* Xs, long strideXs, int N, int Np, int kernel_id, const KernHyp* hyp, const double* Xc, int c0,
-                           int Cn, int Cpad, const double* alpha, double* Kstar, long ldk, long strideK, double* meanpart, double* meanlo,
-                           int nsplit, int m, int store_k, hipStream_t s, int jbase, int mtot) {
-  dim3 grid((unsigned)((Cpad + 511) / 512), (unsigned)nsplit, (unsigned)m);   // 256 threads x 2 columns
-  const int kid = kernel_id <= 1 ? 0 : kernel_id;
-#define LAUNCH(KID, ST)                                                                                                        \
-  BOCF_LAUNCH((cross_kernel<D, KID, ST>), grid, dim3(256), 0, s, Xs, strideXs, N, Np, kernel_id, hyp, Xc, c0, Cn, alpha, \
-                     Kstar, ldk, strideK, meanpart, meanlo, nsplit, Cpad, store_k, jbase, mtot)
-#define BYSTORE(KID)                          \
-  if (store_k == 0) LAUNCH(KID, 0);           \
-  else if (store_k == 1) LAUNCH(KID, 1);      \
-  else LAUNCH(KID, 2)
-  if (kid == 0) { BYSTORE(0); }
-  else if (kid == 2) { BYSTORE(2); }
-  else { BYSTORE(3); }
-#undef BYSTORE
-#undef LAUNCH
-}
-
-static void launch_cross_kernel_run(const double* Xs, long strideXs, int N, int Np, int d, int kernel_id, const KernHyp* hyp, const double* Xc, int c0, int Cn,
-                                    int Cpad, const double* alpha, double* Kstar, long ldk, long strideK, double* meanpart, double* meanlo, int nsplit,
-                                    int m, int store_k, hipStream_t s, int jbase, int mtot);
 void launch_cross_kernel(const double* Xs, long strideXs, int N, int Np, int d, int kernel_id, const KernHyp* hyp, const double* Xc,
                          int c0, int Cn, int Cpad, const double* alpha, double* Kstar, long ldk, long strideK, double* meanpart,
                          double* meanlo, int nsplit, int m, int store_k, hipStream_t s, const int* kids) {
-  int jbase = 0, mtot = m;
-  if (kids) {
-    const int* none = nullptr;
-    bocf_family_runs(kernel_id, kids, m, [&](int j0, int mr, int kid_) {
-      // K* of a run starts at its first output (fp64 or fp32 storage: strideK counts ELEMENTS of the stored type)
-      double* kst = !Kstar ? nullptr : (store_k == 2 ? reinterpret_cast<double*>(reinterpret_cast<float*>(Kstar) + (long)j0 * strideK) : Kstar + (long)j0 * strideK);
-      launch_cross_kernel_run(Xs + (long)j0 * strideXs, strideXs, N, Np, d, kid_, hyp + j0, Xc, c0, Cn, Cpad, alpha + (long)j0 * Np, kst, ldk, strideK,
-                              meanpart, meanlo, nsplit, mr, store_k, s, j0, m);
+  bocf_family_runs(kernel_id, kids, m, [&](int j0, int mr, int kid) {
+    // K* of a run starts at its first output (fp64 or fp32 storage: strideK counts ELEMENTS of the stored type)
+    double* kst = !Kstar ? nullptr : (store_k == 2 ? reinterpret_cast<double*>(reinterpret_cast<float*>(Kstar) + (long)j0 * strideK) : Kstar + (long)j0 * strideK);
+    const dim3 grid((unsigned)((Cpad + 511) / 512), (unsigned)nsplit, (unsigned)mr);   // 256 threads x 2 columns
+    bocf_launch_by_d("cross_kernel", d, [&](auto Dc) {
+      bocf_dispatch_family(kid, [&](auto Kc) {
+        constexpr int D = decltype(Dc)::value, KID = decltype(Kc)::value;
+#define LAUNCH(STORE)                                                                                                                       \
+  BOCF_LAUNCH((cross_kernel<D, KID, STORE>), grid, dim3(256), 0, s, Xs + (long)j0 * strideXs, strideXs, N, Np, hyp + j0, Xc, c0, Cn,        \
+              alpha + (long)j0 * Np, kst, ldk, strideK, meanpart, meanlo, nsplit, Cpad, store_k, j0, m)
+        if (store_k == 0) LAUNCH(0);
+        else if (store_k == 1) LAUNCH(1);
+        else LAUNCH(2);
+#undef LAUNCH
+      });
     });
-    (void)none;
-    return;
-  }
-  launch_cross_kernel_run(Xs, strideXs, N, Np, d, kernel_id, hyp, Xc, c0, Cn, Cpad, alpha, Kstar, ldk, strideK, meanpart, meanlo, nsplit, m, store_k, s,
-                          jbase, mtot);
-}
-
-static void launch_cross_kernel_run(const double* Xs, long strideXs, int N, int Np, int d, int kernel_id, const KernHyp* hyp, const double* Xc, int c0, int Cn,
-                             int Cpad, const double* alpha, double* Kstar, long ldk, long strideK, double* meanpart, double* meanlo, int nsplit,
-                             int m, int store_k, hipStream_t s, int jbase, int mtot) {
-#define CASE(D)                                                                                                                  \
-  case D:                                                                                                                        \
-    launch_cross_d<D>(Xs, strideXs, N, Np, kernel_id, hyp, Xc, c0, Cn, Cpad, alpha, Kstar, ldk, strideK, meanpart, meanlo, nsplit, m, \
-                      store_k, s, jbase, mtot);                                                                                               \
-    break;
-  switch (d) {
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15)
-    CASE(16) CASE(17) CASE(18) CASE(19) CASE(20) CASE(21) CASE(22) CASE(23) CASE(24) CASE(25) CASE(26) CASE(27) CASE(28) CASE(29)
-    CASE(30) CASE(31) CASE(32)
-    default: break;
-  }
-#undef CASE
+  });
 }
 
 // mean[j][c0 + c] = sum_blk meanpart[blk][j][c] + ymean_j   (gp.py:393-399, normalizer.py:67-68)
@@ -249,7 +201,7 @@ __global__ void cov_column_kernel(const double* __restrict__ Xc, int C, int d, i
     const double dq = Xc[(long)c * d + q] / h.ls[q] - Xc[q] / h.ls[q];
     r2 += dq * dq;
   }
-  double v = kern_of_r2_p(kernel_id, h.variance, r2) - (t[(long)j * ldt + c] - h.ymean);
+  double v = kern_of_r2(kernel_id, h.variance, r2) - (t[(long)j * ldt + c] - h.ymean);
   if (c == 0 && (flags & BOCF_ADD_NOISE)) v += h.noise;
   if ((flags & BOCF_CLIP) && !(v >= 1e-10)) v = 1e-10;
   cov[(long)j * ldcov + c] = v;
@@ -304,8 +256,7 @@ void launch_finalize_var(const double* sumsq, int nrt, int Cpad, const KernHyp* 
 // Input gradients of the posterior:
 //   d mu / dx   = sum_i alpha_i      dk(x, X_i)/dx        GP.posterior_mean_gradient      gp.py:438-461
 //   d var / dx  = sum_i -2 w_i       dk(x, X_i)/dx        GP.posterior_variance_gradient  gp.py:464-490, w = Ky^-1 k(X, x)
-// with dk/dx_q = f(r) (x_q - X_iq) / l_q^2, f = invdist * dK_dr (stationary.py:312-331, se.py:135-148):
-//   RBF/SE  -k(r);   Matern52  -(5/3) s2 (1 + sqrt5 r) e^{-sqrt5 r};   Matern32  -3 s2 e^{-sqrt3 r}.
+// with dk/dx_q = kern_dfac(r) (x_q - X_iq) / l_q^2 (kern_family.h).
 // One workgroup per (candidate, output); lanes stride the training points; fixed-order reduction.
 template <int D>
 __global__ __launch_bounds__(256) void grad_kernel(const double* __restrict__ Xs, long strideXs, int N, int Np, int kernel_id,
@@ -368,26 +319,14 @@ void launch_grad_kernel(const double* Xs, long strideXs, int N, int Np, int d, i
                         int Cn, const double* alpha, const double* W, long ldw, long strideW, double* dmean, double* dvar, long ldg,
                         int m, hipStream_t s, const int* kids) {
   if (Cn == 0) return;
-  if (kids) {
-    bocf_family_runs(kernel_id, kids, m, [&](int j0, int mr, int kid_) {
-      launch_grad_kernel(Xs + (long)j0 * strideXs, strideXs, N, Np, d, kid_, hyp + j0, Xc, c0, Cn, alpha + (long)j0 * Np, W + (long)j0 * strideW, ldw, strideW,
-                         dmean + (long)j0 * ldg * d, dvar + (long)j0 * ldg * d, ldg, mr, s, nullptr);
+  bocf_family_runs(kernel_id, kids, m, [&](int j0, int mr, int kid) {
+    const dim3 grid((unsigned)Cn, (unsigned)mr);
+    bocf_launch_by_d("grad_kernel", d, [&](auto Dc) {
+      constexpr int D = decltype(Dc)::value;
+      BOCF_LAUNCH(grad_kernel<D>, grid, dim3(256), 0, s, Xs + (long)j0 * strideXs, strideXs, N, Np, kid, hyp + j0, Xc, c0, alpha + (long)j0 * Np,
+                  W + (long)j0 * strideW, ldw, strideW, dmean + (long)j0 * ldg * d, dvar + (long)j0 * ldg * d, ldg);
     });
-    return;
-  }
-  dim3 grid((unsigned)Cn, (unsigned)m);
-#define CASE(D)                                                                                                                   \
-  case D:                                                                                                                         \
-    BOCF_LAUNCH(grad_kernel<D>, grid, dim3(256), 0, s, Xs, strideXs, N, Np, kernel_id, hyp, Xc, c0, alpha, W, ldw, strideW, \
-                       dmean, dvar, ldg);                                                                                         \
-    break;
-  switch (d) {
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15)
-    CASE(16) CASE(17) CASE(18) CASE(19) CASE(20) CASE(21) CASE(22) CASE(23) CASE(24) CASE(25) CASE(26) CASE(27) CASE(28) CASE(29)
-    CASE(30) CASE(31) CASE(32)
-    default: break;
-  }
-#undef CASE
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -520,7 +459,7 @@ __global__ __launch_bounds__(256) void cross_small_kernel(const double* __restri
           const double d0 = xr[q] - xc[c][q];
           r0 += d0 * d0;
         }
-        v0 = kern_of_r2_p(KID, h.variance, r0);
+        v0 = kern_of_r2(KID, h.variance, r0);
       }
       Kj[(long)kk * ldk + c] = v0;
       kv[row][c] = v0;
@@ -539,36 +478,18 @@ __global__ __launch_bounds__(256) void cross_small_kernel(const double* __restri
   }
 }
 
-template <int D>
-static void launch_cross_small_d(const double* Xs, long strideXs, int N, int Np, int kernel_id, const KernHyp* hyp, const double* Xc, int c0, int Cn, int nc,
-                                 const double* alpha, double* Kstar, long ldk, long strideK, double* meanpart, double* meanlo, int Cpad, int m, hipStream_t s,
-                                 int jbase, int mtot) {
-  const dim3 grid((unsigned)(Np / BOCF_TILE), (unsigned)m);
-  const int kid = kernel_id <= 1 ? 0 : kernel_id;
-#define LAUNCH(KID) BOCF_LAUNCH((cross_small_kernel<D, KID>), grid, dim3(256), 0, s, Xs, strideXs, N, Np, hyp, Xc, c0, Cn, nc, alpha, Kstar, ldk, strideK, \
-                                meanpart, meanlo, Cpad, jbase, mtot)
-  if (kid == 0) LAUNCH(0);
-  else if (kid == 2) LAUNCH(2);
-  else LAUNCH(3);
-#undef LAUNCH
-}
-
 void launch_cross_small(const double* Xs, long strideXs, int N, int Np, int d, int kernel_id, const KernHyp* hyp, const double* Xc, int c0, int Cn, int nc,
                         const double* alpha, double* Kstar, long ldk, long strideK, double* meanpart, double* meanlo, int Cpad, int m, hipStream_t s,
                         const int* kids) {
-  bocf_family_runs(kernel_id, kids, m, [&](int j0, int mr, int kid_) {
-#define CASE(D)                                                                                                                                  \
-  case D:                                                                                                                                        \
-    launch_cross_small_d<D>(Xs + (long)j0 * strideXs, strideXs, N, Np, kid_, hyp + j0, Xc, c0, Cn, nc, alpha + (long)j0 * Np, Kstar + (long)j0 * strideK, ldk, \
-                            strideK, meanpart, meanlo, Cpad, mr, s, j0, m);                                                                        \
-    break;
-    switch (d) {
-      CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15) CASE(16)
-      CASE(17) CASE(18) CASE(19) CASE(20) CASE(21) CASE(22) CASE(23) CASE(24) CASE(25) CASE(26) CASE(27) CASE(28) CASE(29) CASE(30) CASE(31)
-      CASE(32)
-      default: break;
-    }
-#undef CASE
+  bocf_family_runs(kernel_id, kids, m, [&](int j0, int mr, int kid) {
+    const dim3 grid((unsigned)(Np / BOCF_TILE), (unsigned)mr);
+    bocf_launch_by_d("cross_small_kernel", d, [&](auto Dc) {
+      bocf_dispatch_family(kid, [&](auto Kc) {
+        constexpr int D = decltype(Dc)::value, KID = decltype(Kc)::value;
+        BOCF_LAUNCH((cross_small_kernel<D, KID>), grid, dim3(256), 0, s, Xs + (long)j0 * strideXs, strideXs, N, Np, hyp + j0, Xc, c0, Cn, nc,
+                    alpha + (long)j0 * Np, Kstar + (long)j0 * strideK, ldk, strideK, meanpart, meanlo, Cpad, j0, m);
+      });
+    });
   });
 }
 

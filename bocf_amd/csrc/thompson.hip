@@ -5,7 +5,7 @@
 //   thompson_util_kernel  u(s, c) = U(theta_s, F[:, c, s]) with the acquisitions' utility_eval
 // fp64 throughout.
 #include "bocf_internal.h"
-#include "fit_device.h"
+#include "kern_family.h"
 #include "utility_dev.h"
 
 typedef double v4d __attribute__((ext_vector_type(4)));
@@ -165,14 +165,11 @@ void launch_post_cov(const double* V1, long ld1, long strideV1, const double* V2
     g.nrt = (n1 + TBM - 1) / TBM; g.nct = (n2 + TBM - 1) / TBM;
     const unsigned tiles = sym ? (unsigned)(g.nct * (g.nct + 1) / 2) : (unsigned)(g.nrt * g.nct);
     const dim3 grid(tiles, 1, (unsigned)mr);
-    const int k = kid <= 1 ? 0 : kid;
-#define PC(KID)                                                                            \
-  if (sym) BOCF_LAUNCH((post_cov_f64_kernel<KID, true>), grid, dim3(256), 0, s, g);        \
-  else BOCF_LAUNCH((post_cov_f64_kernel<KID, false>), grid, dim3(256), 0, s, g)
-    if (k == 0) { PC(0); }
-    else if (k == 2) { PC(2); }
-    else { PC(3); }
-#undef PC
+    bocf_dispatch_family(kid, [&](auto Kc) {
+      constexpr int KID = decltype(Kc)::value;
+      if (sym) BOCF_LAUNCH((post_cov_f64_kernel<KID, true>), grid, dim3(256), 0, s, g);
+      else BOCF_LAUNCH((post_cov_f64_kernel<KID, false>), grid, dim3(256), 0, s, g);
+    });
   });
 }
 
