@@ -71,6 +71,10 @@ SIGNATURES = {
     "bocf_posterior_samples": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p]),
     "bocf_thompson_select": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int, _c_ll_p,
                                             _c_double_p]),
+    "bocf_set_paths": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int, ctypes.c_int]),
+    "bocf_path_values": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p]),
+    "bocf_path_utility": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int,
+                                         ctypes.POINTER(ctypes.c_int), _c_double_p, _c_double_p]),
     "bocf_set_ref_points": (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int]),
     "bocf_cov_to_ref": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, _c_double_p]),
     "bocf_conditioned_variance": (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p]),

@@ -16,7 +16,7 @@ import time
 
 import numpy as np
 
-from .acquisition_optimizer import ContextManager, _bounds_of, samples_multidimensional_uniform
+from .acquisition_optimizer import ContextManager, _bounds_of, lbfgsb_batched, samples_multidimensional_uniform
 from .recommend import current_marginal_argmaxes
 
 
@@ -66,6 +66,68 @@ class CompositeThompsonBatch(object):
         Z = {h: np.random.normal(size=(model.output_dim, self.n_candidates, int(np.sum(groups == h)))) for h in sorted(set(groups.tolist()))}
         idx, _ = model.thompson_topk(Xc, thetas, groups, Z, utility, q)
         return np.vstack((x0, Xc[distinct_picks(idx)]))
+
+
+class CompositePathwiseThompsonBatch(object):
+    """q suggestions per iteration by Thompson sampling on the composite objective with sample paths that are FUNCTIONS of x
+    (model.draw_paths: Matheron's rule with random Fourier features).  The first point is acquisition.optimize's, as in Sequential
+    (batch_size = 1 is Sequential).  Each of the q - 1 others is a path's argmax of U(theta_s, f_s(.)): the paths score a random design of
+    n_candidates points (no candidate covariance is formed, so the design is as large as any acquisition's), path s takes its best
+    candidate not taken by an earlier path (model.pathwise_topk gives each path its top q), and with `refine` all picks are refined at
+    once by the batched L-BFGS-B inside the space's bounds on the paths' own value and gradient (model.path_utility, one device call per
+    step).  A refined point is kept only where its path utility is not lower than its pick's and it does not repeat an earlier point of
+    the batch; `last_refinement` records picks, refined points and both utilities.
+    Draws from np.random, in this order: the design (samples_multidimensional_uniform, one np.random.uniform per dimension), theta for
+    all paths (utility.parameter_dist.sample(q - 1)), then model.draw_paths(q - 1, n_features): per hyper-sample used, in increasing h,
+    per output the frequencies z (F, d), chi2 (F,) for the Matern kernels only, the phases b (F,), the weights w (F, paths of h) and the
+    noise draws E (N, paths of h).  Path s uses hyper-sample s mod min(10, number_of_hyps_samples()).
+    Given the frequencies a path's mean is the posterior mean exactly; its variance is that of the feature approximation."""
+
+    def __init__(self, acquisition, batch_size, n_candidates=65536, n_features=1024, refine=True):
+        if int(batch_size) < 1:
+            raise ValueError("batch_size must be >= 1")
+        if int(batch_size) > int(n_candidates) or int(batch_size) > 64:
+            raise ValueError("batch_size must be <= min(n_candidates, 64)")
+        if int(n_features) < 1:
+            raise ValueError("n_features must be >= 1")
+        self.acquisition = acquisition
+        self.batch_size = int(batch_size)
+        self.n_candidates = int(n_candidates)
+        self.n_features = int(n_features)
+        self.refine = bool(refine)
+        self.last_refinement = None
+
+    def compute_batch(self, duplicate_manager=None, context_manager=None, x_baseline=None):
+        x0, _ = self.acquisition.optimize(x_baseline=x_baseline)
+        x0 = np.atleast_2d(x0)
+        q = self.batch_size
+        if q == 1:
+            return x0
+        model, utility = self.acquisition.model, self.acquisition.utility
+        P = q - 1
+        bounds = _bounds_of(self.acquisition.space)
+        Xc = samples_multidimensional_uniform(bounds, self.n_candidates)
+        thetas = np.asarray(utility.parameter_dist.sample(P), dtype=float).reshape(P, -1)
+        groups = np.arange(P) % min(10, model.number_of_hyps_samples())
+        model.draw_paths(P, self.n_features)
+        idx, _ = model.pathwise_topk(Xc, thetas, groups, utility, q)
+        picks = Xc[distinct_picks(idx)]
+        if not self.refine:
+            return np.vstack((x0, picks))
+        paths = np.arange(P)
+        u_pick = np.asarray(model.path_utility(picks, paths, thetas, utility), dtype=float)
+
+        def f_df(X, rows):
+            v, g = model.path_utility(X, paths[rows], thetas, utility, grad=True)
+            return -np.asarray(v), -np.asarray(g)
+        refined, _ = lbfgsb_batched(f_df, picks, bounds, with_rows=True)
+        u_ref = np.asarray(model.path_utility(refined, paths, thetas, utility), dtype=float)
+        batch, kept = [x0[0]], np.zeros(P, dtype=bool)
+        for s in range(P):
+            kept[s] = bool(u_ref[s] >= u_pick[s]) and not any(np.array_equal(refined[s], b) for b in batch)
+            batch.append(refined[s] if kept[s] else picks[s])
+        self.last_refinement = {"picks": picks, "pick_values": u_pick, "refined": refined, "refined_values": u_ref, "kept": kept}
+        return np.vstack(batch)
 
 
 class CompositeGreedyBatch(object):

@@ -200,6 +200,11 @@ struct bocf_ctx {
   int pd_r = 0, pd_S = 0;    // pending points resident (0 = none) and the samples F, G were made for
   DevBuf pd_XP, pd_VP, pd_Wp, pd_muP, pd_cov, pd_pack, pd_QFG, pd_par, pd_best, pd_T, pd_muc, pd_E;
   std::vector<double> pd_host, pd_up;   // Sigma(P, P) | mu(P) as copied back; Q | F | G as uploaded (kept: the upload is asynchronous)
+  // ---- pathwise posterior samples (capi_paths.hip): per hyper-sample h one block omega (m', F, d) | phase (m', F) | w (m', F, S) |
+  // v (m', Np, BOCF_TILE) with pt_S[h] paths of pt_F[h] features (pt_S[h] = 0: none); staging and per-call scratch of their own
+  std::vector<DevBuf> pt_buf;
+  std::vector<int> pt_S, pt_F;
+  DevBuf pt_E, pt_g, pt_rhs, pt_tmp, pt_nug, pt_par, pt_rows, pt_tab, pt_pv, pt_pg, pt_val, pt_grad;
 };
 
 // util_prog.hip: what every entry point checks before it evaluates the resident program (utility kind BOCF_UTIL_PROGRAM): one is resident,
@@ -211,6 +216,8 @@ void bocf_thompson_drop(bocf_ctx* c);
 void bocf_kg_drop(bocf_ctx* c);
 // the resident pending points belong to one posterior, like the reference set: dropped wherever it is
 void bocf_pending_drop(bocf_ctx* c);
+// the resident paths belong to one posterior INCLUDING its targets: dropped by every fit and data change (NOT by a candidate upload)
+void bocf_paths_drop(bocf_ctx* c);
 // capi_kg.hip, shared with capi_pending.hip.  A staged point set of the look-ahead paths: the uKG reference set or the pending points.
 struct KgRefSet { const DevBuf* XA; const DevBuf* VA; const DevBuf* Wa; int na; };
 int bocf_kg_stage(bocf_ctx* c, const double* Xdev, int na, int nap, double* VA, double* Wa, double* muA, double* s2A);

@@ -379,6 +379,45 @@ void launch_thompson_util(const double* F, int m, int C, int S, int util_kind, c
                           long ldu, hipStream_t s, const UtilProg* prog = nullptr);
 
 // ---------------------------------------------------------------------------------------
+// pathwise posterior samples (paths.hip)
+// ---------------------------------------------------------------------------------------
+// out[j][c][s] = (add_mean ? ymean_j : 0) + sum_{i < N} k_j(x_c, X_i) v[j][i][s] + sum_{f < F} sqrt(2 s2_j / F) cos(omega_jf . x_c / l_j + b_jf) w[j][f][s]
+// for the launch's m outputs, C points and S <= 64 paths; per point the sum runs over i ascending, then f ascending, whatever the batch.
+struct PathValArgs {
+  const double* Xs; long strideXs; int N;           // scaled training inputs (N, d) per output; N = 0: the feature part alone
+  const double* v; long ldv; long strideV;          // (rows, ldv) per output, the first S columns read (nullptr with N = 0)
+  const double* omega; const double* phase; const double* w; int F;   // (m, F, d), (m, F), (m, F, S) contiguous
+  int S, nt;                                        // nt = ceil(S / 16): set by the launcher
+  const KernHyp* hyp;
+  const double* Xc; long strideXc; int prescaled;   // points (C, d): shared and divided by the lengthscales here, or (prescaled) per output and used as they are
+  int C;
+  double* out; long strideOut;                      // (C, S) per output
+  int add_mean;
+};
+void launch_path_values(const PathValArgs& a, int d, int kernel_id, const int* kids, int m, hipStream_t s);
+// rhs[j][i][s] = yc[j][i] - gX[j][i][s] - sqrt(nug_j) E[j][i][s] for i < N, s < S, zero elsewhere (Np x ld per output); gX, E: (m, N, S)
+void launch_path_rhs(const double* yc, const double* gX, const double* E, const double* nug, int N, int Np, int S, int ld, double* rhs, int m, hipStream_t s);
+// the resident paths of one hyper-sample as the small kernels see them (device pointers to its first output)
+struct PathHyper {
+  const double* omega; const double* phase; const double* w; const double* v;
+  int F, S, p0, h;                                  // p0: global index of its first path
+};
+struct PathPointArgs {
+  const double* Xs; long strideXs; int N, Np;       // of ALL outputs of the model
+  const KernHyp* hyp; const int* kids; int kernel_id;   // kids: device array of the m kernel ids, or nullptr = kernel_id
+  const PathHyper* tab; int nh;                     // device table of the hyper-samples with paths, p0 ascending
+  int per; long ldv;
+  const double* Xc; const int* row_path;            // (C, d) rows and their global path
+  double* pv; double* pg;                           // (C, per) values (target mean included) and (C, per, d) input gradients
+};
+void launch_path_point(const PathPointArgs& a, int d, int C, hipStream_t s);
+// val[c] = U(theta_{row_path[c]}, pv[c]) and (grad != nullptr) grad[c][q] = sum_j dU/dy_j pg[c][j][q]; theta rows tw wide
+void launch_path_chain(const double* pv, const double* pg, int per, int d, int C, const int* row_path, int util_kind, const double* theta, int tw,
+                       const double* params, double* val, double* grad, hipStream_t s, const UtilProg* prog = nullptr);
+void launch_path_chain_prog(const double* pv, const double* pg, int d, int C, const int* row_path, const double* theta, int theta_dim, double* val,
+                            double* grad, const UtilProg& p, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------
 // look-ahead posterior and discrete composite knowledge gradient (kg.hip)
 // ---------------------------------------------------------------------------------------
 // out[j][c] = variance_j - sum_{kk < K} V[j][kk][c]^2 for c < n: the raw (noiseless, unclipped) posterior variance from V = R^T K(X, x_c)

@@ -95,6 +95,7 @@ extern "C" void bocf_destroy(bocf_ctx* c) {
   if (c->ts_helper) bocf_destroy(c->ts_helper);
   c->ts_helper = nullptr;
   for (DevBuf& b : c->ts_F) b.release();
+  for (DevBuf& b : c->pt_buf) b.release();
   drop_events(c);
   drop_phases(c);
   if (c->pin_in) (void)hipHostFree(c->pin_in);
@@ -111,7 +112,8 @@ extern "C" void bocf_destroy(bocf_ctx* c) {
                     &c->ts_X, &c->ts_K, &c->ts_V, &c->ts_mp, &c->ts_mu, &c->ts_Z, &c->ts_jit, &c->ts_u, &c->ts_theta, &c->ts_params, &c->ts_out,
                     &c->kg_XA, &c->kg_VA, &c->kg_Wa, &c->kg_muA, &c->kg_s2A, &c->kg_nug, &c->kg_V, &c->kg_W, &c->kg_cov, &c->kg_s2c, &c->kg_dcov, &c->kg_dmean, &c->kg_dvar,
                     &c->kg_par, &c->kg_v0, &c->kg_astar, &c->kg_AB, &c->kg_out, &c->kg_dout, &c->prog_buf,
-                    &c->pd_XP, &c->pd_VP, &c->pd_Wp, &c->pd_muP, &c->pd_cov, &c->pd_pack, &c->pd_QFG, &c->pd_par, &c->pd_best, &c->pd_T, &c->pd_muc, &c->pd_E};
+                    &c->pd_XP, &c->pd_VP, &c->pd_Wp, &c->pd_muP, &c->pd_cov, &c->pd_pack, &c->pd_QFG, &c->pd_par, &c->pd_best, &c->pd_T, &c->pd_muc, &c->pd_E,
+                    &c->pt_E, &c->pt_g, &c->pt_rhs, &c->pt_tmp, &c->pt_nug, &c->pt_par, &c->pt_rows, &c->pt_tab, &c->pt_pv, &c->pt_pg, &c->pt_val, &c->pt_grad};
   for (DevBuf* b : bufs) b->release();
   if (c->infer_out) (void)hipHostFree(c->infer_out);
   if (c->tile_ctr) (void)hipFree(c->tile_ctr);
@@ -257,6 +259,7 @@ extern "C" int bocf_set_posterior(bocf_ctx* c, int m, int C, int N, const double
   bocf_thompson_drop(c);
   bocf_kg_drop(c);
   bocf_pending_drop(c);
+  bocf_paths_drop(c);
   c->fitted = true;
   c->canned = true;
   c->have_acq = false;

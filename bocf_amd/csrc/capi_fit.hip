@@ -71,7 +71,7 @@ static int check_fit_input(bocf_ctx* c, const char* who, const FitInput& in) {
 
 // The factor R changes (a new model, an appended observation): every copy and product made FROM R is stale -- the fp32 and int8 copies
 // of the predict pass, the Ky^-1 = R R^T an inference's schedule left in the T scratch -- and so is what was staged or scored with the
-// old posterior: the acquisition vector, the Thompson samples, the reference set (uKG) and the pending points.  THE one place: a new
+// old posterior: the acquisition vector, the Thompson samples, the reference set (uKG), the pending points and the sample paths.  THE one place: a new
 // derived copy of R is dropped here, and both bocf_append and every new model go through it.
 static void factor_changed(bocf_ctx* c) {
   c->r32_valid = false; c->ri8_valid = false;
@@ -80,6 +80,7 @@ static void factor_changed(bocf_ctx* c) {
   bocf_thompson_drop(c);
   bocf_kg_drop(c);
   bocf_pending_drop(c);
+  bocf_paths_drop(c);
 }
 
 // A new resident model of in's shape: the previous fit and everything derived from it are gone, the pending kernel ids are taken.
@@ -572,6 +573,7 @@ static int refresh_targets(bocf_ctx* c, const double* Y, double* lml_out) {
   bocf_thompson_drop(c);
   bocf_kg_drop(c);
   bocf_pending_drop(c);
+  bocf_paths_drop(c);
   const std::vector<double> yc = centre_targets(c, Y, c->N, Np, m);
   HIPCHK(hipMemcpyAsync(c->hypd.p, c->hyp.data(), sizeof(KernHyp) * m, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(c->yc.p, yc.data(), sizeof(double) * (size_t)m * Np, hipMemcpyHostToDevice, c->stream));

@@ -400,3 +400,43 @@ void launch_thompson_util_prog(const double* F, int C, int S, const double* thet
   BOCF_LAUNCH(thompson_util_prog_kernel, dim3((unsigned)((C + nt - 1) / nt), (unsigned)S), dim3((unsigned)nt), lds, s, F, C, S, theta, theta_dim, u, ldu,
               dev_view(p));
 }
+
+// ---------------------------------------------------------------------------------------------
+// Utility of a row's path values and the chain rule (path_chain_kernel): a thread per row, the value+gradient section when a gradient is
+// wanted (it also leaves U), else the value section
+__global__ __launch_bounds__(256) void path_chain_prog_kernel(const double* __restrict__ pv, const double* __restrict__ pg, int d, int C,
+                                                              const int* __restrict__ row_path, const double* __restrict__ theta, int theta_dim,
+                                                              double* __restrict__ val, double* __restrict__ grad, UtilProgDev p) {
+  const int nt = blockDim.x;
+  const int c = blockIdx.x * nt + threadIdx.x;
+  const int cc = min(c, C - 1);                            // every thread runs the program: the branches stay uniform
+  double* file = prog_file + threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < BOCF_MAX_M; ++j)
+    if (j < p.m) file[(long)j * nt] = pv[(long)cc * p.m + j];
+  const double* th = theta + (long)row_path[cc] * theta_dim;
+  if (!grad) {
+    prog_run(p.val_code, p.n_val, file, nt, p.m, th, p.consts);
+    if (c < C) val[c] = file[(long)(p.m + p.val_out) * nt];
+    return;
+  }
+  prog_run(p.grad_code, p.n_grad, file, nt, p.m, th, p.consts);
+  if (c >= C) return;
+  val[c] = file[(long)(p.m + p.grad_out[0]) * nt];
+  for (int q = 0; q < d; ++q) {
+    double t = 0.0;
+#pragma unroll
+    for (int j = 0; j < BOCF_MAX_M; ++j)
+      if (j < p.m) t += file[(long)(p.m + p.grad_out[1 + j]) * nt] * pg[((long)c * p.m + j) * d + q];
+    grad[(long)c * d + q] = t;
+  }
+}
+
+void launch_path_chain_prog(const double* pv, const double* pg, int d, int C, const int* row_path, const double* theta, int theta_dim, double* val,
+                            double* grad, const UtilProg& p, hipStream_t s) {
+  int nt;
+  size_t lds;
+  util_prog_geometry(p, &nt, &lds);
+  BOCF_LAUNCH(path_chain_prog_kernel, dim3((unsigned)((C + nt - 1) / nt)), dim3((unsigned)nt), lds, s, pv, pg, d, C, row_path, theta, theta_dim, val, grad,
+              dev_view(p));
+}

@@ -20,9 +20,9 @@ class _Resident(object):
     """THE record of what the host believes is resident on the device -- a new resident buffer is a field here, and the events that
     invalidate it name it in their forget() call; nowhere else.  None = unknown / not resident.
     candidates: their count; W, Z, reference, pending: key of the uploaded set_mc_samples / set_eu_samples / set_reference_points /
-    set_pending_points arrays; program: the utility program blob; query, gradient: (key, arrays) of the last all-hyper-sample posterior query, served per h as
+    set_pending_points arrays; paths: the record of draw_paths (fit serial, device group and device order of every path); program: the utility program blob; query, gradient: (key, arrays) of the last all-hyper-sample posterior query, served per h as
     slices."""
-    __slots__ = ("candidates", "W", "Z", "program", "reference", "pending", "query", "gradient")
+    __slots__ = ("candidates", "W", "Z", "program", "reference", "pending", "paths", "query", "gradient")
 
     def __init__(self):
         self.forget()
@@ -198,7 +198,7 @@ class multi_outputGP(object):
         if len(Y) != self.output_dim or any(y.shape[0] != X.shape[0] for y in Y):
             raise ValueError("Y_all must hold output_dim arrays of N observations")
         prevX = self._X
-        self._resident.forget("candidates", "reference", "pending")      # every model change drops the device's reference set and pending points
+        self._resident.forget("candidates", "reference", "pending", "paths")      # every model change drops the device's reference set, pending points and paths
         self._X, self._Y = X.copy(), [y[:, None].copy() for y in Y]
         self._Ymat = None
         self._ibuf = None
@@ -277,7 +277,7 @@ class multi_outputGP(object):
         it are gone.  With M, a positive return raises jitchol's error for the outputs that failed."""
         _ffi.check(rc, what)
         self._fitted = False
-        self._resident.forget("W", "Z", "program", "candidates")
+        self._resident.forget("W", "Z", "program", "candidates", "paths")
         if M is not None and rc > 0:   # jitchol gave up (GPy/util/linalg.py:71) for the outputs whose last rung still has a bad pivot
             err = np.linalg.LinAlgError("not positive definite, even with jitter.")
             err.outputs = self._failed_outputs(M)
@@ -296,7 +296,7 @@ class multi_outputGP(object):
         self._fit_key = self._hyper_key()
         self._fitted = True
         self._fit_serial += 1
-        self._resident.forget("query", "gradient")
+        self._resident.forget("query", "gradient", "paths")
 
     # ---- hyper-parameter learning: GPModel._create_model / updateModel (gpmodel.py:50-128) ------------------------
     def _create_sampler_state(self):
@@ -833,6 +833,129 @@ class multi_outputGP(object):
             order += [s for h in hs for s in np.flatnonzero(path_groups == h)]
         order = np.asarray(order, dtype=int)
         pa, n_pa, th, tdim, _, _ = self._utility_args(params, thetas[order], None)
+        idx = np.empty((P, k), dtype=np.int64)
+        val = np.empty((P, k))
+        _ffi.check(_ffi.load().bocf_thompson_select(self._context().handle, kind, pa, n_pa, th, tdim, int(k), idx.ctypes.data_as(_ffi._c_ll_p),
+                                                    _ffi.dptr(val)), "bocf_thompson_select")
+        out_idx, out_val = np.empty_like(idx), np.empty_like(val)
+        out_idx[order], out_val[order] = idx, val
+        return out_idx, out_val
+
+    # ---- pathwise posterior samples: Thompson paths as functions --------------------------------------------------------------
+    def _path_groups(self, n_paths):
+        """Hyper-sample of path s: s mod min(10, number_of_hyps_samples()) (the acquisitions' hyper-sample count)."""
+        return np.arange(int(n_paths)) % min(10, self.number_of_hyps_samples())
+
+    def draw_paths(self, n_paths, n_features=1024):
+        """Draw and stage n_paths posterior sample paths f_s(.) of all outputs (Matheron's rule with n_features random Fourier features per
+        output, bocf_set_paths); path s belongs to hyper-sample s mod min(10, number_of_hyps_samples()).  A path is a function: it stays
+        resident through every candidate upload and is dropped with the posterior (updateModel, refits).  Given the frequencies the
+        path mean is the posterior mean exactly; the path variance is that of the feature approximation of the prior.
+        np.random draw order: per device hyper-sample used, in increasing h (one, holding every path, with fixed hyper-parameters): per
+        output j: z = normal(F, d); for the Matern kernels only chi2 = chisquare(2 nu, F) (omega = z / sqrt(chi2 / (2 nu)), nu = 5/2 or 3/2);
+        b = uniform(0, 2 pi, F); w = normal(F, S_h); E = normal(N, S_h), with S_h the number of paths of h."""
+        self._ensure_fitted()
+        n_paths, F = int(n_paths), int(n_features)
+        if n_paths < 1 or F < 1:
+            raise ValueError("n_paths and n_features must be >= 1")
+        groups = self._path_groups(n_paths)
+        dev = groups if self._H > 1 else np.zeros(n_paths, dtype=int)
+        kids = self._hyper_arrays()[0]
+        N, d = self._X.shape
+        m = self.output_dim
+        lib, ctx = _ffi.load(), self._context()
+        self._resident.forget("paths")
+        _ffi.check(lib.bocf_set_paths(ctx.handle, -1, None, None, None, None, F, 0), "bocf_set_paths")     # (the paths of an earlier draw are gone)
+        order, counts = [], {}
+        for g in sorted(set(dev.tolist())):
+            mine = np.flatnonzero(dev == g)
+            S = mine.size
+            om, ph, w, E = np.empty((m, F, d)), np.empty((m, F)), np.empty((m, F, S)), np.empty((m, N, S))
+            for j in range(m):
+                z = np.random.normal(size=(F, d))
+                nu = {_ffi.KERN_MATERN52: 2.5, _ffi.KERN_MATERN32: 1.5}.get(int(kids[g * m + j]))
+                if nu is not None:
+                    z = z / np.sqrt(np.random.chisquare(2.0 * nu, size=F) / (2.0 * nu))[:, None]
+                om[j] = z
+                ph[j] = np.random.uniform(0.0, 2.0 * np.pi, size=F)
+                w[j] = np.random.normal(size=(F, S))
+                E[j] = np.random.normal(size=(N, S))
+            _ffi.check(lib.bocf_set_paths(ctx.handle, int(g), _ffi.dptr(om), _ffi.dptr(ph), _ffi.dptr(w), _ffi.dptr(E), F, S), "bocf_set_paths")
+            order += mine.tolist()
+            counts[int(g)] = S
+        self._resident.paths = {"serial": self._fit_serial, "n": n_paths, "features": F, "groups": groups, "order": np.asarray(order, dtype=int),
+                                "counts": counts}
+
+    def _paths(self):
+        rec = self._resident.paths
+        if rec is None or rec["serial"] != self._fit_serial:
+            raise RuntimeError("no paths resident for this fit: call draw_paths")
+        return rec
+
+    def _path_values(self, rec, keep_out):
+        """One bocf_path_values call per hyper-sample with paths, at the resident candidates; (m, n, P) in path order, or None."""
+        n = self._resident.candidates
+        out = np.empty((self.output_dim, n, rec["n"])) if keep_out else None
+        at = 0
+        for g in sorted(rec["counts"]):
+            S = rec["counts"][g]
+            blk = np.empty((self.output_dim, n, S)) if keep_out else None
+            _ffi.check(_ffi.load().bocf_path_values(self._context().handle, g, _ffi.dptr(blk)), "bocf_path_values")
+            if keep_out:
+                out[:, :, rec["order"][at:at + S]] = blk
+            at += S
+        return out
+
+    def path_values(self, X):
+        """The resident paths at X (n, d): (m, n, n_paths), [j, i, s] = f_js(X_i) (target mean included)."""
+        rec = self._paths()
+        self._set_candidates(np.atleast_2d(X))
+        return self._path_values(rec, True)
+
+    def path_utility(self, X, row_path, thetas, utility, grad=False):
+        """u_i = U(thetas[row_path[i]], f_{., row_path[i]}(X_i)) for the rows of X (n, d), each on ONE resident path (bocf_path_utility);
+        thetas (n_paths, theta_dim), one row per path.  Returns u (n,), or (u (n,), du/dX (n, d)) with grad=True."""
+        rec = self._paths()
+        thetas = _ffi.f64(np.asarray(thetas, dtype=float).reshape(rec["n"], -1))
+        rows = np.asarray(row_path, dtype=int).reshape(-1)
+        if rows.size and (rows.min() < 0 or rows.max() >= rec["n"]):
+            raise IndexError("row_path out of range (0 .. n_paths - 1)")
+        kind = utility.device_kind(self.output_dim)
+        if kind == _ffi.UTIL_PROGRAM:
+            self.set_utility_program(utility.program_blob)
+        n = self._set_candidates(np.atleast_2d(X))
+        if n != rows.size:
+            raise ValueError("row_path must hold one path index per row of X")
+        inv = np.empty(rec["n"], dtype=int)
+        inv[rec["order"]] = np.arange(rec["n"])                 # path s -> the device's path number
+        dev_rows = np.ascontiguousarray(inv[rows], dtype=np.int32)
+        pa, n_pa, th, tdim, _, _ = self._utility_args(utility.device_params, thetas[rec["order"]], None)
+        val = np.empty(n)
+        dval = np.empty((n, self._X.shape[1])) if grad else None
+        if n:
+            _ffi.check(_ffi.load().bocf_path_utility(self._context().handle, kind, pa, n_pa, th, tdim, rec["n"],
+                                                     dev_rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _ffi.dptr(val), _ffi.dptr(dval)),
+                       "bocf_path_utility")
+        return (val, dval) if grad else val
+
+    def pathwise_topk(self, X, thetas, path_groups, utility, k):
+        """The twin of thompson_topk on the resident paths of draw_paths: path s (of hyper-sample path_groups[s], which must be the
+        hyper-sample it was drawn for) ranks the candidate set X (C, d) by U(thetas[s], f_s(c)).  One value call per hyper-sample used,
+        one selection call; no C x C covariance, so C is not capped by it.  Returns (idx (P, k), val (P, k)) in path order, value
+        descending, ties to the lowest index."""
+        rec = self._paths()
+        path_groups = np.asarray(path_groups, dtype=int)
+        if path_groups.shape != rec["groups"].shape or np.any(path_groups != rec["groups"]):
+            raise ValueError("path_groups are not the hyper-samples the resident paths were drawn for (draw_paths)")
+        P = rec["n"]
+        thetas = _ffi.f64(np.asarray(thetas, dtype=float).reshape(P, -1))
+        kind = utility.device_kind(self.output_dim)
+        if kind == _ffi.UTIL_PROGRAM:
+            self.set_utility_program(utility.program_blob)
+        self._set_candidates(X)
+        self._path_values(rec, False)
+        order = rec["order"]
+        pa, n_pa, th, tdim, _, _ = self._utility_args(utility.device_params, thetas[order], None)
         idx = np.empty((P, k), dtype=np.int64)
         val = np.empty((P, k))
         _ffi.check(_ffi.load().bocf_thompson_select(self._context().handle, kind, pa, n_pa, th, tdim, int(k), idx.ctypes.data_as(_ffi._c_ll_p),

@@ -297,6 +297,38 @@ int bocf_posterior_samples(bocf_ctx* ctx, int group, const double* Z, int S, int
 int bocf_thompson_select(bocf_ctx* ctx, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim, int k,
                          long long* idx_out, double* val_out);
 
+/* Pathwise posterior samples: Thompson paths as FUNCTIONS of x (Matheron's rule with random Fourier features; Wilson et al. 2020,
+ * "Efficiently sampling functions from Gaussian process posteriors").  Local to the context and for a fitted model only, like the joint
+ * posterior above; `group` has the meaning it has in bocf_posterior_samples.  Per output j (of hyper-sample h) and path s, with the
+ * inputs divided by the lengthscales, x~ = x / l_j:
+ *   phi_jf(x) = sqrt(2 s2_j / F) cos(omega_jf . x~ + b_jf)                       f < F
+ *   g_js(x)   = sum_f phi_jf(x) w_jfs                                            a draw of the (feature-approximated) prior
+ *   v_js      = Ky_j^-1 (yc_j - g_js(X) - sqrt(nug_j) E_j[:, s]),                nug_j = noise_j + 1e-8 + jitter_j, the fit's diagonal
+ *   f_js(x)   = ybar_j + g_js(x) + sum_i k_j(x, X_i) v_js[i]
+ * The device consumes no random numbers: omega (M_g, F, d), phase b (M_g, F), weights w (M_g, F, S) and eps E (M_g, N, S) come from the
+ * host.  For the RBF / SE ids omega ~ N(0, I); for Matern-nu omega = z / sqrt(chi2_{2 nu} / (2 nu)), z ~ N(0, I) (nu = 5/2, 3/2);
+ * b ~ U[0, 2 pi); w, E ~ N(0, 1).
+ * EXACT given (omega, b): E_{w,E}[f] is the posterior mean, and at the training inputs f_s(X_i) = Y_i - sqrt(nug) E_is - nug v_is.
+ * APPROXIMATE: the variance of a path is that of the feature approximation of the prior (the method's error, not the device's; F = 2048
+ * on Matern-5/2 gave pointwise ratios between 0.73 and 2.07 to the exact posterior variance near data).
+ *
+ * bocf_set_paths: stages S paths (1 <= S <= 64) of F features (1 <= F <= 16384) for the hyper-samples of `group`, replacing theirs; S = 0
+ *   drops them.  The solve is v = R (R^T rhs) with the fit's R = U^-1 through the fp64 GEMM: a PLAIN fp64 solve, no double-double
+ *   refinement (the posterior mean's alpha is refined; v is not).  Paths belong to one posterior INCLUDING its targets: bocf_fit,
+ *   bocf_infer, bocf_append and bocf_update_targets drop them; bocf_set_candidates does NOT -- a path is a function.
+ * bocf_path_values: evaluates every resident path of the group at the resident candidates; values_out (M_g, C, S) or NULL.  The values
+ *   stay on the device as the group's resident Thompson samples, so bocf_thompson_select ranks them unchanged (and a new candidate set
+ *   drops the VALUES, as it drops any samples).  Per candidate the sum runs over the training rows in increasing order, then the
+ *   features: a candidate's value does not depend on the batch it came in.  The predict and acquisition state is left as it was.
+ * bocf_path_utility: for row c of the resident candidates, u_c = U(theta_p, f_{., p}(x_c)) of the ONE path p = row_path[c] -- paths
+ *   numbered as bocf_thompson_select numbers them -- and (grad_out (C, d) != NULL) du_c/dx = sum_j dU/dy_j df_{j,p}/dx.  theta
+ *   (P, theta_dim) with P the number of resident paths; val_out (C).  Meant for the few hundred rows of a refinement step.
+ * Every failure returns < 0 with bocf_last_error() naming the entry point; the context stays usable. */
+int bocf_set_paths(bocf_ctx* ctx, int group, const double* omega, const double* phase, const double* weights, const double* eps, int F, int S);
+int bocf_path_values(bocf_ctx* ctx, int group, double* values_out);
+int bocf_path_utility(bocf_ctx* ctx, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim, int P,
+                      const int* row_path, double* val_out, double* grad_out);
+
 /* Input gradients of the posterior at the resident candidates, (m,C,d) each.  Replaces
  * multi_outputGP.posterior_mean_gradient / posterior_variance_gradient (multi_outputGP.py:284-306) ->
  * GP.posterior_mean_gradient / posterior_variance_gradient (GPy/core/gp.py:438-490) -> kern.gradients_X
