@@ -84,6 +84,10 @@ SIGNATURES = {
     "bocf_get_pending_samples": (ctypes.c_int, [_ctx_p, _c_double_p]),
     "bocf_acq_pending": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int,
                                         _c_double_p, _c_double_p]),
+    "bocf_set_output_constraints": (ctypes.c_int, [_ctx_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int, ctypes.c_int]),
+    "bocf_feasible_best": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int, _c_double_p, _c_ll_p]),
+    "bocf_acq_mc_constrained": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int,
+                                               _c_double_p, _c_double_p]),
     "bocf_mean_at_train": (ctypes.c_int, [_ctx_p, _c_double_p]),
     "bocf_acq_linear_grad": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p]),
     "bocf_acq_mc_grad": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p,

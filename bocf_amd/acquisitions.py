@@ -397,6 +397,61 @@ class uEI_pending(uEI_noiseless):
         return np.reshape(acqX, (X.shape[0], 1)), np.reshape(dacq_dX, X.shape)
 
 
+class uEI_constrained(uEI_noiseless):
+    """uEI_noiseless under linear constraints on the outputs (constraints.OutputConstraints):
+
+        alpha(x) = sum_l p_l (1/S) sum_s I_ls(x) phi(y_s(x)),   phi(y) = prod_k s(-(A y - b)_k / eta_k),
+
+    s the logistic function, y_s(x) = mu(x) + sigma(x) o W_s the parent's samples, I_ls the improvement over the best FEASIBLE training
+    point (hard test on the posterior mean), or 1 when no training point is feasible -- the acquisition is then the smoothed probability
+    of feasibility.  The constraints read the same outputs as the utility, so they are applied sample by sample on the device
+    (bocf_acq_mc_constrained); value and gradient are those of the same smooth function.
+
+    Parameter conventions and np.random touchpoints are the parent's.  There is no host fallback: a utility without a compiled-in device
+    kind raises NotImplementedError."""
+    _model_entry = "acq_mc_constrained"
+
+    def __init__(self, model, space, optimizer=None, cost_withGradients=None, utility=None, constraints=None):
+        super(uEI_constrained, self).__init__(model, space, optimizer, cost_withGradients=cost_withGradients, utility=utility)
+        if constraints is None or not hasattr(constraints, "feasible"):
+            raise TypeError("uEI_constrained needs constraints=OutputConstraints(A, b, eta)")
+        if constraints.m != self.model.output_dim:
+            raise ValueError("the constraints are on %d outputs, the model has %d" % (constraints.m, self.model.output_dim))
+        self.constraints = constraints
+
+    def _constrained_kind(self):
+        try:
+            kind = self.utility.device_kind(self.model.output_dim)
+        except NotImplementedError:
+            kind = None
+        if kind is None or kind == _ffi.UTIL_PROGRAM:
+            raise NotImplementedError("uEI_constrained needs a utility with a compiled-in device kind (Utility(..., device=...): %s): the "
+                                      "constraints are applied inside the device's Monte-Carlo sum, there is no host loop and no utility program"
+                                      % ", ".join(COMPILED_IN))
+        return kind
+
+    def _evaluate(self, X, samples, prob, grad):
+        kind = self._constrained_kind()
+        model = self._device_model()
+        model.set_output_constraints(self.constraints)       # (free when this set is the resident one)
+        return model.acq_mc_constrained(X, kind, self.utility.device_params, device_thetas(kind, samples), prob, W=self.W_samples,
+                                        n_hyps=self.n_hyps_samples, grad=grad)
+
+    def _compute_acq(self, X, parallel=True):
+        X = np.atleast_2d(X)
+        prob = self.utility_prob_dist if self.use_full_support else None
+        return np.reshape(self._evaluate(X, self.utility_params_samples, prob, False), (X.shape[0], 1))
+
+    def _compute_acq_withGradients(self, X):
+        X = np.atleast_2d(X)
+        if self.use_full_support:
+            samples2, prob = self.utility.parameter_dist.support, self.utility_prob_dist
+        else:
+            samples2, prob = self.utility.parameter_dist.sample(1), None
+        acqX, dacq_dX = self._evaluate(X, samples2, prob, True)
+        return np.reshape(acqX, (X.shape[0], 1)), np.reshape(dacq_dX, X.shape)
+
+
 class uPI(_MonteCarlo):
     analytical_gradient_prediction = False
     _kind = _ffi.ACQ_PI

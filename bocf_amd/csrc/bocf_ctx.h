@@ -205,6 +205,13 @@ struct bocf_ctx {
   std::vector<DevBuf> pt_buf;
   std::vector<int> pt_S, pt_F;
   DevBuf pt_E, pt_g, pt_rhs, pt_tmp, pt_nug, pt_par, pt_rows, pt_tab, pt_pv, pt_pg, pt_val, pt_grad;
+  // ---- linear output constraints of the constrained acquisition (capi_constrained.hip): the table A (K, m') | b (K) | 1 / eta (K), resident
+  // until it is replaced (they do not depend on the factor: no fit, data change or candidate upload drops them); parameters, feasible
+  // incumbents (Ha, L) and feasible counts (Ha) of a call in buffers of their own -- the acquisitions' parameter and best-so-far caches
+  // are left as they were
+  int cq_K = 0, cq_m = 0;    // constraints resident (0 = none) and the outputs per hyper-sample they were given for
+  DevBuf cq_tab, cq_par, cq_best, cq_nf;
+  std::vector<double> cq_up; // theta | prob | utility parameters as uploaded (kept: the upload is asynchronous)
 };
 
 // util_prog.hip: what every entry point checks before it evaluates the resident program (utility kind BOCF_UTIL_PROGRAM): one is resident,
@@ -229,6 +236,11 @@ int bocf_kg_chunk_dcov(bocf_ctx* c, const KgRefSet& ref, int j0, int mg, int c0,
 int bocf_check_posterior(bocf_ctx* c, const char* who);
 int bocf_group_range(bocf_ctx* c, const char* who, int group, int* j0, int* mg, int* per);
 int bocf_enqueue_V(bocf_ctx* c, int j0, int mg, const double* Xq, int n, int npad, double* V, double* mu);
+// capi.hip, shared with capi_constrained.hip: the posterior the Monte-Carlo acquisitions read (variance with noise, clipped at 1e-10; with
+// grad its input gradients) of every resident candidate, through the predict pass's plan and chunking; and two device vectors to the host
+// with ONE synchronisation (either may be empty)
+int bocf_acq_posterior(bocf_ctx* c, bool grad);
+int bocf_copy_pair_out(bocf_ctx* c, const void* src0, double* out0, size_t b0, const void* src1, double* out1, size_t b1);
 
 
 // HIP-event bracket of a named phase on the context's stream (only with option "profile" = 1; otherwise free)

@@ -488,3 +488,26 @@ size_t pending_table_bytes(const PendArgs& a);
 void launch_pending_threshold(const PendArgs& a, hipStream_t s);
 void launch_pending_acq(const PendArgs& a, hipStream_t s);
 void launch_pending_grad(const PendArgs& a, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------
+// constrained Monte-Carlo expected improvement: linear output constraints inside the sample sum (cacq.hip)
+// ---------------------------------------------------------------------------------------
+#define BOCF_MAX_CONSTRAINTS 8
+struct CacqArgs {
+  const double* mean; const double* var; long ld;   // (m, ld) rows of one hyper-sample, first C columns valid
+  const double* dmean; const double* dvar; long ldg; int d;   // gradient form: (m, ldg, d)
+  int m, C, L, S, K;
+  int util_kind, theta_dim;
+  const double* theta; const double* prob;          // device (L, theta_dim), (L)
+  const double* best; const long long* nfeas;       // device (L) feasible incumbent and |F| of this hyper-sample (launch_feasible_best)
+  const double* util_params;                        // (BOCF_MAX_M)
+  const double* Wt;                                 // (m, S) transposed common random numbers
+  const double* tab;                                // A (K, m) | b (K) | 1 / eta (K)
+  double* acq; double* dacq;                        // (C), (C, d)
+  int accumulate; double scale;                     // written, or added to (hyper-sample h > 0); 1 / H
+};
+// best[l] = max over the training points with A mu - b <= 0 (every row) of U(theta_l, mu), -inf when there is none; nfeas[0] = their number
+void launch_feasible_best(const double* mu_train, int N, int m, int util_kind, const double* theta, int theta_dim, int L, const double* util_params,
+                          const double* tab, int K, double* best, long long* nfeas, hipStream_t s);
+void launch_cacq(const CacqArgs& a, hipStream_t s);
+void launch_cacq_grad(const CacqArgs& a, hipStream_t s);

@@ -1,0 +1,158 @@
+// Constrained-acquisition entry points of the C ABI (include/bocf_hip.h): bocf_set_output_constraints, bocf_feasible_best,
+// bocf_acq_mc_constrained -- the Monte-Carlo expected improvement of the composite utility with K <= 8 linear constraints on the outputs
+// weighing every sample (kernels: cacq.hip).  The posterior is the one bocf_acq_mc reads (the predict pass's plan and chunking, variance
+// with noise, clipped), the hyper-sample loop runs here under options acq_hyper_samples / best_group, the value is left as the context's
+// acquisition vector for the selections.  The constraints do not depend on the factor: nothing here calls a drop function, and no fit,
+// data change or candidate upload forgets them.  The feasible incumbent is computed per call into buffers of this path (the
+// acquisitions' parameter and best-so-far caches are left as they were).  One stream, one synchronisation per call.
+#include "bocf_ctx.h"
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+extern "C" int bocf_set_output_constraints(bocf_ctx* c, const double* A, const double* b, const double* eta, int K, int m) {
+  static const char* who = "bocf_set_output_constraints";
+  // (the argument checks come first: they need no context, so no GPU)
+  if (K == 0) {                                              // drop them
+    if (!c) return fail(who, "null context");
+    c->cq_K = 0;
+    return 0;
+  }
+  if (K < 1 || K > BOCF_MAX_CONSTRAINTS) return fail(who, "K out of range (1 .. 8; 0 drops the constraints)");
+  if (m < 1 || m > BOCF_MAX_M) return fail(who, "m out of range (1 .. 16)");
+  if (!A || !b || !eta) return fail(who, "null A, b or eta");
+  for (int i = 0; i < K * m; ++i)
+    if (!std::isfinite(A[i])) return fail(who, "A has a non-finite entry");
+  for (int k = 0; k < K; ++k) {
+    if (!std::isfinite(b[k])) return fail(who, "b has a non-finite entry");
+    if (!std::isfinite(eta[k]) || !(eta[k] > 0.0)) return fail(who, "eta must be finite and > 0");
+  }
+  if (!c) return fail(who, "null context");
+  if (c->fitted) {
+    const int H = c->hyper_samples > 0 ? c->hyper_samples : 1;
+    if (c->m % H == 0 && c->m / H != m) return fail(who, "m differs from the outputs per hyper-sample of the fitted model");
+  }
+  HIPCHK(hipSetDevice(c->device));
+  std::vector<double> tab((size_t)K * m + 2 * (size_t)K);
+  memcpy(tab.data(), A, sizeof(double) * (size_t)K * m);
+  for (int k = 0; k < K; ++k) {
+    tab[(size_t)K * m + k] = b[k];
+    tab[(size_t)K * m + K + k] = 1.0 / eta[k];
+  }
+  if (c->cq_tab.ensure(sizeof(double) * ((size_t)BOCF_MAX_CONSTRAINTS * BOCF_MAX_M + 2 * BOCF_MAX_CONSTRAINTS))) return -1;
+  c->cq_K = 0;                                               // (replaced below, or gone if this call fails)
+  HIPCHK(hipMemcpyAsync(c->cq_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->cq_K = K;
+  c->cq_m = m;
+  return 0;
+}
+
+// the checks the two evaluating entry points share, in their order (errors name `who`): outputs per hyper-sample, or -1
+static int constrained_checks(bocf_ctx* c, const char* who, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim,
+                              int L) {
+  if (!c || !c->fitted) return fail(who, "model not fitted");
+  if (util_kind == BOCF_UTIL_PROGRAM)
+    return fail(who, "the constrained acquisition does not take a utility program (BOCF_UTIL_PROGRAM): use one of the compiled-in utilities");
+  if (util_kind < BOCF_UTIL_LINEAR || util_kind > BOCF_UTIL_ROSENBROCK) return fail(who, "unknown utility kind");
+  if (c->cq_K < 1) return fail(who, "no output constraints resident (bocf_set_output_constraints)");
+  const int H = c->hyper_samples > 0 ? c->hyper_samples : 1;
+  if (c->m % H) return fail(who, "the fitted outputs are not a whole number of hyper-samples (option hyper_samples)");
+  const int m = c->m / H;
+  if (m > BOCF_MAX_M) return fail(who, "more outputs per hyper-sample than the device utilities take (16)");
+  if (c->cq_m != m) return fail(who, "the resident output constraints were given for another m than the outputs per hyper-sample");
+  if (c->best_group >= H) return fail(who, "option best_group is not a valid hyper-sample index");
+  if (L < 1 || L > BOCF_MAX_L) return fail(who, "L out of range (1 .. 32)");
+  if (theta_dim < 1 || theta_dim > BOCF_MAX_M || !theta) return fail(who, "theta must be (L, 1 <= theta_dim <= 16)");
+  if ((util_kind == BOCF_UTIL_LINEAR || util_kind == BOCF_UTIL_NEG_SQ_DIST) && theta_dim != m) return fail(who, "theta_dim must equal m");
+  if (util_kind == BOCF_UTIL_ROSENBROCK && (m & 1)) return fail(who, "rosenbrock utility needs even m");
+  if (n_util_params < 0 || n_util_params > BOCF_MAX_M || (n_util_params > 0 && !util_params)) return fail(who, "bad utility parameters");
+  if (util_kind == BOCF_UTIL_NEG_EXP_COS && n_util_params != m) return fail(who, "neg_exp_cos needs m weights");
+  return m;
+}
+
+// theta | prob | utility parameters in one upload (out of c->cq_up, which outlives the asynchronous copy); the incumbent buffers
+static int constrained_upload(bocf_ctx* c, const double* util_params, int n_util_params, const double* theta, int theta_dim, const double* prob, int L,
+                              int Ha) {
+  const size_t nth = (size_t)L * theta_dim, npar = nth + L + BOCF_MAX_M;
+  c->cq_up.assign(npar, 0.0);
+  memcpy(c->cq_up.data(), theta, sizeof(double) * nth);
+  for (int l = 0; l < L; ++l) c->cq_up[nth + l] = prob ? prob[l] : 1.0 / L;
+  for (int i = 0; i < n_util_params; ++i) c->cq_up[nth + L + i] = util_params[i];
+  if (c->cq_par.ensure(sizeof(double) * npar) || c->cq_best.ensure(sizeof(double) * (size_t)Ha * L) || c->cq_nf.ensure(sizeof(long long) * (size_t)Ha)) return -1;
+  HIPCHK(hipMemcpyAsync(c->cq_par.p, c->cq_up.data(), sizeof(double) * npar, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+
+extern "C" int bocf_feasible_best(bocf_ctx* c, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim, int L,
+                                  double* best_out, long long* n_feasible_out) {
+  static const char* who = "bocf_feasible_best";
+  const int m = constrained_checks(c, who, util_kind, util_params, n_util_params, theta, theta_dim, L);
+  if (m < 0) return -1;
+  HIPCHK(hipSetDevice(c->device));
+  if (constrained_upload(c, util_params, n_util_params, theta, theta_dim, nullptr, L, 1)) return -1;
+  const double* th = c->cq_par.as<double>();
+  const int gb = c->best_group >= 0 ? c->best_group : 0;
+  launch_feasible_best(c->mu_train.as<double>() + (size_t)gb * m * c->N, c->N, m, util_kind, th, theta_dim, L, th + (size_t)L * theta_dim + L,
+                       c->cq_tab.as<double>(), c->cq_K, c->cq_best.as<double>(), c->cq_nf.as<long long>(), c->stream);
+  long long nf = 0;
+  std::vector<double> best(L);
+  HIPCHK(hipMemcpyAsync(best.data(), c->cq_best.p, sizeof(double) * L, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(&nf, c->cq_nf.p, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  LAUNCHCHK();
+  if (best_out) memcpy(best_out, best.data(), sizeof(double) * L);
+  if (n_feasible_out) *n_feasible_out = nf;
+  return 0;
+}
+
+extern "C" int bocf_acq_mc_constrained(bocf_ctx* c, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim,
+                                       const double* prob, int L, double* acq_out, double* dacq_out) {
+  static const char* who = "bocf_acq_mc_constrained";
+  const int m = constrained_checks(c, who, util_kind, util_params, n_util_params, theta, theta_dim, L);
+  if (m < 0) return -1;
+  if (c->S_mc < 1) return fail(who, "no Monte-Carlo samples set (bocf_set_mc_samples)");
+  if (c->C < 1) return fail(who, "no resident candidates (bocf_set_candidates)");
+  const bool grad = dacq_out != nullptr;
+  if (grad && c->canned) return fail(who, "the context holds a host-given posterior (bocf_set_posterior): it carries no gradients; fit first");
+  if (grad && c->d > 64) return fail(who, "input dimension too large");
+  const int H = c->hyper_samples > 0 ? c->hyper_samples : 1;
+  const int Ha = (c->acq_hyper_samples > 0 && c->acq_hyper_samples < H) ? c->acq_hyper_samples : H;
+  HIPCHK(hipSetDevice(c->device));
+  if (constrained_upload(c, util_params, n_util_params, theta, theta_dim, prob, L, Ha)) return -1;
+  c->have_acq = false;
+  if (bocf_acq_posterior(c, grad)) return -1;
+  const size_t nth = (size_t)L * theta_dim;
+  CacqArgs a{};
+  a.ld = c->pred_cap; a.m = m; a.C = c->C; a.L = L; a.S = c->S_mc; a.K = c->cq_K; a.util_kind = util_kind; a.theta_dim = theta_dim;
+  a.theta = c->cq_par.as<double>(); a.prob = a.theta + nth; a.util_params = a.prob + L;
+  a.Wt = c->Wt.as<double>(); a.tab = c->cq_tab.as<double>(); a.acq = c->acq.as<double>(); a.scale = 1.0 / Ha;
+  if (grad) { a.ldg = c->pred_cap; a.d = c->d; a.dacq = c->dacq.as<double>(); }
+  // the hyper-sample loop of bocf_acq_mc: hyper-sample h reads rows [h m, (h + 1) m) of the posterior and adds its share; the incumbent
+  // is each hyper-sample's own, or that of option best_group for all
+  for (int h = 0; h < Ha; ++h) {
+    const int slot = c->best_group >= 0 ? 0 : h;
+    double* best = c->cq_best.as<double>() + (size_t)slot * L;
+    long long* nf = c->cq_nf.as<long long>() + slot;
+    PhaseTimer t(c, "acq");
+    if (h == 0 || c->best_group < 0) {
+      const int gb = c->best_group >= 0 ? c->best_group : h;
+      launch_feasible_best(c->mu_train.as<double>() + (size_t)gb * m * c->N, c->N, m, util_kind, a.theta, theta_dim, L, a.util_params, a.tab, a.K, best, nf,
+                           c->stream);
+    }
+    a.best = best; a.nfeas = nf;
+    a.mean = c->mean.as<double>() + (size_t)h * m * a.ld;
+    a.var = c->var.as<double>() + (size_t)h * m * a.ld;
+    if (grad) {
+      a.dmean = c->dmean.as<double>() + (size_t)h * m * a.ldg * a.d;
+      a.dvar = c->dvar.as<double>() + (size_t)h * m * a.ldg * a.d;
+    }
+    a.accumulate = h > 0;
+    if (grad) launch_cacq_grad(a, c->stream);
+    else launch_cacq(a, c->stream);
+  }
+  c->have_acq = true;
+  const size_t b0 = acq_out ? sizeof(double) * (size_t)c->C : 0, b1 = grad ? sizeof(double) * (size_t)c->C * c->d : 0;
+  return bocf_copy_pair_out(c, c->acq.p, acq_out, b0, c->dacq.p, dacq_out, b1);
+}

@@ -21,8 +21,9 @@ class _Resident(object):
     invalidate it name it in their forget() call; nowhere else.  None = unknown / not resident.
     candidates: their count; W, Z, reference, pending: key of the uploaded set_mc_samples / set_eu_samples / set_reference_points /
     set_pending_points arrays; paths: the record of draw_paths (fit serial, device group and device order of every path); program: the utility program blob; query, gradient: (key, arrays) of the last all-hyper-sample posterior query, served per h as
-    slices."""
-    __slots__ = ("candidates", "W", "Z", "program", "reference", "pending", "paths", "query", "gradient")
+    slices; constraints: key of the set_output_constraints set (it does not depend on the fit: no model change forgets it, only pickling
+    -- a new context -- does)."""
+    __slots__ = ("candidates", "W", "Z", "program", "reference", "pending", "paths", "query", "gradient", "constraints")
 
     def __init__(self):
         self.forget()
@@ -761,6 +762,64 @@ class multi_outputGP(object):
         dacq = np.empty((n, self._X.shape[1])) if grad else None
         if n:
             _ffi.check(_ffi.load().bocf_acq_pending(self._context().handle, int(util_kind), *util, _ffi.dptr(acq), _ffi.dptr(dacq)), "bocf_acq_pending")
+        return (acq, dacq) if grad else acq
+
+    # ---- linear output constraints and the constrained Monte-Carlo acquisition ---------------------------------------------------
+    def set_output_constraints(self, constraints):
+        """Stage an OutputConstraints (A y - b <= 0, temperatures eta) on the device (bocf_set_output_constraints); None drops the resident
+        set.  The set stays resident until it is replaced: it does not depend on the fit, so updateModel leaves it; re-sending the resident
+        set is free."""
+        self._ensure_fitted()
+        lib, h = _ffi.load(), self._context().handle
+        if constraints is None:
+            _ffi.check(lib.bocf_set_output_constraints(h, None, None, None, 0, self.output_dim), "bocf_set_output_constraints")
+            self._resident.forget("constraints")
+            return
+        if constraints.m != self.output_dim:
+            raise ValueError("the constraints are on %d outputs, the model has %d" % (constraints.m, self.output_dim))
+        key = constraints.key()
+        if key == self._resident.constraints:
+            return
+        self._resident.forget("constraints")
+        _ffi.check(lib.bocf_set_output_constraints(h, _ffi.dptr(constraints.A), _ffi.dptr(constraints.b), _ffi.dptr(constraints.eta), constraints.K,
+                                                   constraints.m), "bocf_set_output_constraints")
+        self._resident.constraints = key
+
+    def _constraints_resident(self):
+        if self._resident.constraints is None:
+            raise RuntimeError("no output constraints resident: call set_output_constraints")
+
+    def feasible_best(self, util_kind, util_params, thetas):
+        """(best (L,), n_feasible): per utility parameter the best U(theta_l, mu(X_i)) over the training points whose posterior mean passes
+        the HARD test A mu - b <= 0 of the resident constraints (-inf when none does), and how many pass (bocf_feasible_best); the
+        posterior mean is that of the current hyper-sample."""
+        self._ensure_fitted()
+        self._constraints_resident()
+        if not self.fixed_hyps:
+            self._context().set_option("best_group", self._current_h)
+        params, n_params, th, tdim, _, L = self._utility_args(util_params, thetas, None)
+        best, nf = np.empty(L), ctypes.c_longlong()
+        _ffi.check(_ffi.load().bocf_feasible_best(self._context().handle, int(util_kind), params, n_params, th, tdim, L, _ffi.dptr(best), ctypes.byref(nf)),
+                   "bocf_feasible_best")
+        return best, int(nf.value)
+
+    def acq_mc_constrained(self, X, util_kind, util_params, thetas, prob, W=None, n_hyps=None, grad=False, fetch=True):
+        """Constrained Monte-Carlo expected improvement of the batch X (n, d) (bocf_acq_mc_constrained): every sample of the uEI sum is
+        weighed by the smoothed feasibility of the resident constraints, the incumbent is the best FEASIBLE training point of the
+        hyper-sample current on entry (none feasible: the smoothed probability of feasibility).  Conventions of acq_mc: W (S, output_dim)
+        are the common random numbers.  Returns alpha (n,), or (alpha (n,), d alpha / dX (n, d)) with grad=True.  The values stay on the
+        device for select_topk (fetch=False returns None)."""
+        self._begin_acq(n_hyps, False)
+        self._constraints_resident()
+        if W is not None:
+            self.set_mc_samples(W)
+        n = self._set_candidates(np.atleast_2d(X))
+        util = self._utility_args(util_params, thetas, prob)
+        acq = np.empty(n) if fetch else None
+        dacq = np.empty((n, self._X.shape[1])) if grad else None
+        if n:
+            _ffi.check(_ffi.load().bocf_acq_mc_constrained(self._context().handle, int(util_kind), *util, _ffi.dptr(acq), _ffi.dptr(dacq)),
+                       "bocf_acq_mc_constrained")
         return (acq, dacq) if grad else acq
 
     # ---- joint posterior and composite Thompson sampling ------------------------------------------------------------------------

@@ -487,6 +487,43 @@ int bocf_get_pending_samples(bocf_ctx* ctx, double* F_out);
 int bocf_acq_pending(bocf_ctx* ctx, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim,
                      const double* prob, int L, double* acq_out, double* dacq_out);
 
+/* ---- constrained uEI: linear constraints on the outputs inside the Monte-Carlo sum.  The simulator's outputs also
+ * decide whether a design is admissible; the constraints are functions of the same m' outputs per hyper-sample the utility reads, so they
+ * are applied sample by sample (the reference's AcquisitionBase has its constraint weighting commented out, base.py:5-74):
+ *   A (K, m'), b (K), eta (K), 1 <= K <= 8, eta_k > 0, every entry finite
+ *   c_k(y)  = sum_j A_kj y_j - b_k                   feasible <=> c_k(y) <= 0 for every k
+ *   s(t)    = 1 / (1 + exp(-t))                      evaluated as exp of a non-positive argument on both branches
+ *   phi(y)  = prod_k s(-c_k(y) / eta_k)              k in index order
+ *   y_s(x)  = mu(x) + sigma(x) o W_s                 mu, sigma exactly the posterior bocf_acq_mc uses (variance with noise, clipped at 1e-10)
+ *   F       = { i : c_k(mu_g(X_i)) <= 0 for every k }    HARD test on the train mean of the hyper-sample option best_group selects
+ *   best_l  = max_{i in F} U(theta_l, mu_g(X_i))     only when F is not empty
+ *   I_ls(x) = max(U(theta_l, y_s) - best_l, 0) if F is not empty;  1 if it is (the acquisition is then the smoothed probability of feasibility)
+ *   alpha(x) = (1/Ha) sum_h sum_l p_l (1/S) sum_s I_ls(x) phi(y_s(x))
+ * and, with T_ls = I_ls phi and s_k = s(-c_k / eta_k),
+ *   dT/dy_j = [F not empty] 1{U > best_l} dU/dy_j phi - T_ls sum_k (1 - s_k) A_kj / eta_k
+ *   A_j = sum_l p_l (1/S) sum_s dT/dy_j,  B_j = sum_l p_l (1/S) sum_s dT/dy_j W_sj / (2 sigma_j)
+ *   d alpha / dx_q = (1/Ha) sum_h sum_j A_j dmu_j/dx_q + B_j dsigma^2_j/dx_q.
+ * The smoothing is in the value as well as in the gradient; eta -> 0 recovers the indicator; a vacuous constraint (b_k huge) gives s = 1
+ * exactly and alpha is then the uEI of bocf_acq_mc.  fp64; every failure returns < 0 with the entry point's name in the error text.
+ *
+ * bocf_set_output_constraints: the constraints stay resident until they are replaced (K = 0 drops them), like the samples of
+ *   bocf_set_mc_samples; they do not depend on the factor, so no fit, append, target update or candidate upload forgets them.  m must be the
+ *   outputs per hyper-sample (checked here when a model is fitted, and by the evaluating calls).
+ * bocf_feasible_best: best_out (L) = best_l (-inf when F is empty) and *n_feasible_out = |F| for the hyper-sample of option best_group
+ *   (-1: hyper-sample 0); either may be NULL.
+ * bocf_acq_mc_constrained: alpha of every resident candidate into acq_out (C) or NULL -- the values are left as the context's acquisition
+ *   vector, so bocf_select_topk, bocf_global_topk and the packed multi-rank merge work on them unchanged; dacq_out (C, d) or NULL = value
+ *   only.  Needs resident constraints and Monte-Carlo samples; theta (L, theta_dim), prob (L) or NULL (= 1 / L); BOCF_UTIL_PROGRAM is
+ *   refused, and so is the gradient form on a bocf_set_posterior context.  The hyper-sample loop runs inside the call under options
+ *   acq_hyper_samples and best_group exactly as in bocf_acq_mc (-1: every hyper-sample's own feasible incumbent); candidate batches of any
+ *   size go through the predict pass's chunking.  The incumbent is computed per call in buffers of this path: the parameter and
+ *   best-so-far caches of the other acquisitions, the pending, reference and path sets are left as they were.  One synchronisation. */
+int bocf_set_output_constraints(bocf_ctx* ctx, const double* A, const double* b, const double* eta, int K, int m);
+int bocf_feasible_best(bocf_ctx* ctx, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim,
+                       int L, double* best_out, long long* n_feasible_out);
+int bocf_acq_mc_constrained(bocf_ctx* ctx, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim,
+                            const double* prob, int L, double* acq_out, double* dacq_out);
+
 /* ---- multi-GPU: candidate shards, ONE collective.  One process per GPU, one context per process.  The
  * reference's own candidate parallelism is a pathos process pool over single candidates (uEI_noiseless.py:85-97); here rank
  * r scores the contiguous slice [lo_r, hi_r) of the batch against its resident fit and the ranks exchange only their k
