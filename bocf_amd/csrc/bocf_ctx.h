@@ -10,7 +10,6 @@
 #include <utility>
 #include <vector>
 
-int bocf_fail(const char* what, const char* detail);      // records bocf_last_error(), returns -1
 void bocf_set_error(const char* text);                    // records bocf_last_error() verbatim (positive LAPACK-style returns)
 int bocf_launch_status();
 int bocf_plan_cholesky(bocf_ctx* c, bool kinv, CholPlan* out);   // capi_chol.hip: the schedule of the next factorization (kinv: Ky^-1 wanted), its streams and counters
@@ -211,8 +210,15 @@ struct bocf_ctx {
   // are left as they were
   int cq_K = 0, cq_m = 0;    // constraints resident (0 = none) and the outputs per hyper-sample they were given for
   DevBuf cq_tab, cq_par, cq_best, cq_nf;
-  std::vector<double> cq_up; // theta | prob | utility parameters as uploaded (kept: the upload is asynchronous)
+  UtilPack util_up;          // host source of the utility block's upload (util_args.h says why it lives here); kg_par, pd_par, cq_par are its device copies
 };
+
+// hyper-samples the acquisitions average over: option acq_hyper_samples, or (0, or more than are resident) all of option hyper_samples (1 .. 64)
+static inline int bocf_acq_hyper_count(const bocf_ctx* c) {
+  return (c->acq_hyper_samples > 0 && c->acq_hyper_samples < c->hyper_samples) ? c->acq_hyper_samples : c->hyper_samples;
+}
+// whose best-so-far hyper-sample h improves on: that of option best_group for all, or (-1) its own
+static inline int bocf_best_group_of(const bocf_ctx* c, int h) { return c->best_group >= 0 ? c->best_group : h; }
 
 // util_prog.hip: what every entry point checks before it evaluates the resident program (utility kind BOCF_UTIL_PROGRAM): one is resident,
 // no util_params, and it was built for these m outputs per hyper-sample and this theta_dim.  Errors name `who`.

@@ -3,11 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kern_dispatch.h"     // BOCF_MAX_D (max input dimension), bocf_dispatch_d, bocf_dispatch_family, bocf_family_runs
+#include "util_args.h"         // BOCF_MAX_M (max model outputs per hyper-sample), BOCF_MAX_L (max utility-parameter support size on device)
 
 #define BOCF_TILE 128          // panel width NB == GEMM tile edge; every matrix is padded to it
-#define BOCF_MAX_M 16         // max model outputs (per hyper-sample)
 #define BOCF_MAX_FITS 1024     // max independent factorizations in one fit (hyper-samples x outputs)
-#define BOCF_MAX_L 32          // max utility-parameter support size on device
 
 // Every kernel launch goes through BOCF_LAUNCH: the launch status (bad grid / block / shared-memory configuration) is read
 // right behind the launch and the FIRST failure is remembered with the kernel's name; the C-ABI entry point that issued it

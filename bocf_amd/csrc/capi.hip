@@ -649,11 +649,11 @@ typedef void (*AcqLaunch)(const AcqArgs& a, hipStream_t s);
 // The reference's h-loop (maEI.py:85-97, uEI_noiseless.py:71-82) runs here: hyper-sample h reads rows
 // [h*m, (h+1)*m) of the mean / variance / gradient buffers and adds its share (1/H) to acq (and dacq).
 static void acq_over_hyper_samples(bocf_ctx* c, AcqArgs a, int m, int linear, AcqLaunch launch) {
-  const int H = (c->acq_hyper_samples > 0 && c->acq_hyper_samples < c->hyper_samples) ? c->acq_hyper_samples : c->hyper_samples;
+  const int H = bocf_acq_hyper_count(c);
   const double* mean = a.mean; const double* var = a.var; const double* dmean = a.dmean; const double* dvar = a.dvar;
   for (int h = 0; h < H; ++h) {
     if (h == 0 || c->best_group < 0) {
-      const int gb = c->best_group >= 0 ? c->best_group : h;
+      const int gb = bocf_best_group_of(c, h);
       // one hyper-sample: best-so-far depends on the train mean and the parameters only -- the hundreds of acquisition calls of one
       // BO step (batch call + L-BFGS refinements) share it
       const int sig = (linear ? 1 : 0) | (a.util_kind << 1) | (gb << 8);

@@ -50,51 +50,40 @@ extern "C" int bocf_set_output_constraints(bocf_ctx* c, const double* A, const d
 }
 
 // the checks the two evaluating entry points share, in their order (errors name `who`): outputs per hyper-sample, or -1
-static int constrained_checks(bocf_ctx* c, const char* who, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim,
-                              int L) {
+static int constrained_checks(bocf_ctx* c, const char* who, const UtilArgs& u) {
   if (!c || !c->fitted) return fail(who, "model not fitted");
-  if (util_kind == BOCF_UTIL_PROGRAM)
-    return fail(who, "the constrained acquisition does not take a utility program (BOCF_UTIL_PROGRAM): use one of the compiled-in utilities");
-  if (util_kind < BOCF_UTIL_LINEAR || util_kind > BOCF_UTIL_ROSENBROCK) return fail(who, "unknown utility kind");
+  if (bocf_util_check_kind(who, u, "the constrained acquisition does not take a utility program (BOCF_UTIL_PROGRAM): use one of the compiled-in utilities"))
+    return -1;
   if (c->cq_K < 1) return fail(who, "no output constraints resident (bocf_set_output_constraints)");
-  const int H = c->hyper_samples > 0 ? c->hyper_samples : 1;
+  const int H = c->hyper_samples;
   if (c->m % H) return fail(who, "the fitted outputs are not a whole number of hyper-samples (option hyper_samples)");
   const int m = c->m / H;
   if (m > BOCF_MAX_M) return fail(who, "more outputs per hyper-sample than the device utilities take (16)");
   if (c->cq_m != m) return fail(who, "the resident output constraints were given for another m than the outputs per hyper-sample");
   if (c->best_group >= H) return fail(who, "option best_group is not a valid hyper-sample index");
-  if (L < 1 || L > BOCF_MAX_L) return fail(who, "L out of range (1 .. 32)");
-  if (theta_dim < 1 || theta_dim > BOCF_MAX_M || !theta) return fail(who, "theta must be (L, 1 <= theta_dim <= 16)");
-  if ((util_kind == BOCF_UTIL_LINEAR || util_kind == BOCF_UTIL_NEG_SQ_DIST) && theta_dim != m) return fail(who, "theta_dim must equal m");
-  if (util_kind == BOCF_UTIL_ROSENBROCK && (m & 1)) return fail(who, "rosenbrock utility needs even m");
-  if (n_util_params < 0 || n_util_params > BOCF_MAX_M || (n_util_params > 0 && !util_params)) return fail(who, "bad utility parameters");
-  if (util_kind == BOCF_UTIL_NEG_EXP_COS && n_util_params != m) return fail(who, "neg_exp_cos needs m weights");
+  if (bocf_util_check(who, u, m, BOCF_EU_MC)) return -1;
   return m;
 }
 
-// theta | prob | utility parameters in one upload (out of c->cq_up, which outlives the asynchronous copy); the incumbent buffers
-static int constrained_upload(bocf_ctx* c, const double* util_params, int n_util_params, const double* theta, int theta_dim, const double* prob, int L,
-                              int Ha) {
-  const size_t nth = (size_t)L * theta_dim, npar = nth + L + BOCF_MAX_M;
-  c->cq_up.assign(npar, 0.0);
-  memcpy(c->cq_up.data(), theta, sizeof(double) * nth);
-  for (int l = 0; l < L; ++l) c->cq_up[nth + l] = prob ? prob[l] : 1.0 / L;
-  for (int i = 0; i < n_util_params; ++i) c->cq_up[nth + L + i] = util_params[i];
-  if (c->cq_par.ensure(sizeof(double) * npar) || c->cq_best.ensure(sizeof(double) * (size_t)Ha * L) || c->cq_nf.ensure(sizeof(long long) * (size_t)Ha)) return -1;
-  HIPCHK(hipMemcpyAsync(c->cq_par.p, c->cq_up.data(), sizeof(double) * npar, hipMemcpyHostToDevice, c->stream));
+// theta | prob | utility parameters in one upload; the incumbent buffers
+static int constrained_upload(bocf_ctx* c, const UtilArgs& u, int Ha) {
+  const UtilPack& pk = bocf_util_pack(u, nullptr, 0, &c->util_up);
+  if (c->cq_par.ensure(pk.bytes()) || c->cq_best.ensure(sizeof(double) * (size_t)Ha * u.L) || c->cq_nf.ensure(sizeof(long long) * (size_t)Ha)) return -1;
+  HIPCHK(hipMemcpyAsync(c->cq_par.p, pk.host.data(), pk.bytes(), hipMemcpyHostToDevice, c->stream));
   return 0;
 }
 
 extern "C" int bocf_feasible_best(bocf_ctx* c, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim, int L,
                                   double* best_out, long long* n_feasible_out) {
   static const char* who = "bocf_feasible_best";
-  const int m = constrained_checks(c, who, util_kind, util_params, n_util_params, theta, theta_dim, L);
+  const UtilArgs u{util_kind, util_params, n_util_params, theta, theta_dim, nullptr, L};
+  const int m = constrained_checks(c, who, u);
   if (m < 0) return -1;
   HIPCHK(hipSetDevice(c->device));
-  if (constrained_upload(c, util_params, n_util_params, theta, theta_dim, nullptr, L, 1)) return -1;
-  const double* th = c->cq_par.as<double>();
-  const int gb = c->best_group >= 0 ? c->best_group : 0;
-  launch_feasible_best(c->mu_train.as<double>() + (size_t)gb * m * c->N, c->N, m, util_kind, th, theta_dim, L, th + (size_t)L * theta_dim + L,
+  if (constrained_upload(c, u, 1)) return -1;
+  const double* par = c->cq_par.as<double>();
+  const int gb = bocf_best_group_of(c, 0);
+  launch_feasible_best(c->mu_train.as<double>() + (size_t)gb * m * c->N, c->N, m, util_kind, par + c->util_up.theta, theta_dim, L, par + c->util_up.params,
                        c->cq_tab.as<double>(), c->cq_K, c->cq_best.as<double>(), c->cq_nf.as<long long>(), c->stream);
   long long nf = 0;
   std::vector<double> best(L);
@@ -110,23 +99,23 @@ extern "C" int bocf_feasible_best(bocf_ctx* c, int util_kind, const double* util
 extern "C" int bocf_acq_mc_constrained(bocf_ctx* c, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim,
                                        const double* prob, int L, double* acq_out, double* dacq_out) {
   static const char* who = "bocf_acq_mc_constrained";
-  const int m = constrained_checks(c, who, util_kind, util_params, n_util_params, theta, theta_dim, L);
+  const UtilArgs u{util_kind, util_params, n_util_params, theta, theta_dim, prob, L};
+  const int m = constrained_checks(c, who, u);
   if (m < 0) return -1;
   if (c->S_mc < 1) return fail(who, "no Monte-Carlo samples set (bocf_set_mc_samples)");
   if (c->C < 1) return fail(who, "no resident candidates (bocf_set_candidates)");
   const bool grad = dacq_out != nullptr;
   if (grad && c->canned) return fail(who, "the context holds a host-given posterior (bocf_set_posterior): it carries no gradients; fit first");
   if (grad && c->d > 64) return fail(who, "input dimension too large");
-  const int H = c->hyper_samples > 0 ? c->hyper_samples : 1;
-  const int Ha = (c->acq_hyper_samples > 0 && c->acq_hyper_samples < H) ? c->acq_hyper_samples : H;
+  const int Ha = bocf_acq_hyper_count(c);
   HIPCHK(hipSetDevice(c->device));
-  if (constrained_upload(c, util_params, n_util_params, theta, theta_dim, prob, L, Ha)) return -1;
+  if (constrained_upload(c, u, Ha)) return -1;
   c->have_acq = false;
   if (bocf_acq_posterior(c, grad)) return -1;
-  const size_t nth = (size_t)L * theta_dim;
+  const double* par = c->cq_par.as<double>();
   CacqArgs a{};
   a.ld = c->pred_cap; a.m = m; a.C = c->C; a.L = L; a.S = c->S_mc; a.K = c->cq_K; a.util_kind = util_kind; a.theta_dim = theta_dim;
-  a.theta = c->cq_par.as<double>(); a.prob = a.theta + nth; a.util_params = a.prob + L;
+  a.theta = par + c->util_up.theta; a.prob = par + c->util_up.prob; a.util_params = par + c->util_up.params;
   a.Wt = c->Wt.as<double>(); a.tab = c->cq_tab.as<double>(); a.acq = c->acq.as<double>(); a.scale = 1.0 / Ha;
   if (grad) { a.ldg = c->pred_cap; a.d = c->d; a.dacq = c->dacq.as<double>(); }
   // the hyper-sample loop of bocf_acq_mc: hyper-sample h reads rows [h m, (h + 1) m) of the posterior and adds its share; the incumbent
@@ -137,7 +126,7 @@ extern "C" int bocf_acq_mc_constrained(bocf_ctx* c, int util_kind, const double*
     long long* nf = c->cq_nf.as<long long>() + slot;
     PhaseTimer t(c, "acq");
     if (h == 0 || c->best_group < 0) {
-      const int gb = c->best_group >= 0 ? c->best_group : h;
+      const int gb = bocf_best_group_of(c, h);
       launch_feasible_best(c->mu_train.as<double>() + (size_t)gb * m * c->N, c->N, m, util_kind, a.theta, theta_dim, L, a.util_params, a.tab, a.K, best, nf,
                            c->stream);
     }

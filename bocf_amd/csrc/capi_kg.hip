@@ -4,7 +4,6 @@
 // d sigma^2 / dx from grad_kernel.  fp64 only: options predict_f32 / predict_i8 are not read here.  One stream, one synchronisation per call.
 #include "bocf_ctx.h"
 
-#include <cstring>
 #include <vector>
 
 #define KG_MAX_REF 1024
@@ -194,27 +193,18 @@ extern "C" int bocf_acq_kg(bocf_ctx* c, int mode, int util_kind, const double* u
   static const char* who = "bocf_acq_kg";
   if (bocf_check_posterior(c, who)) return -1;
   if (mode < BOCF_EU_MEAN || mode > BOCF_EU_MC) return fail(who, "unknown mode");
-  if (util_kind == BOCF_UTIL_PROGRAM) return fail(who, "the knowledge gradient does not take a utility program (BOCF_UTIL_PROGRAM): use one of the compiled-in utilities");
-  if (util_kind < BOCF_UTIL_LINEAR || util_kind > BOCF_UTIL_ROSENBROCK) return fail(who, "unknown utility kind");
+  const UtilArgs u{util_kind, util_params, n_util_params, theta, theta_dim, prob, L};
+  if (bocf_util_check_kind(who, u, "the knowledge gradient does not take a utility program (BOCF_UTIL_PROGRAM): use one of the compiled-in utilities")) return -1;
   int j0, mg, m;
   if (bocf_group_range(c, who, -1, &j0, &mg, &m)) return -1;
   if (m > BOCF_MAX_M) return fail(who, "more outputs per hyper-sample than the device utilities take (16)");
-  if (L < 1 || L > BOCF_MAX_L) return fail(who, "L out of range (1 .. 32)");
-  if (theta_dim < 1 || theta_dim > BOCF_MAX_M || !theta) return fail(who, "theta must be (L, 1 <= theta_dim <= 16)");
-  if ((mode == BOCF_EU_MEAN || util_kind == BOCF_UTIL_LINEAR || util_kind == BOCF_UTIL_NEG_SQ_DIST) && theta_dim != m)
-    return fail(who, "theta_dim must equal m");
-  if (mode != BOCF_EU_MEAN && util_kind == BOCF_UTIL_ROSENBROCK && (m & 1)) return fail(who, "rosenbrock utility needs even m");
-  if (mode == BOCF_EU_CLOSED && (util_kind == BOCF_UTIL_LINEAR || util_kind == BOCF_UTIL_NEG_EXP_COS))
-    return fail(who, "no closed-form expectation for this utility (use the Monte-Carlo mode)");
-  if (n_util_params < 0 || n_util_params > BOCF_MAX_M || (n_util_params > 0 && !util_params)) return fail(who, "bad utility parameters");
-  if (mode == BOCF_EU_MC && util_kind == BOCF_UTIL_NEG_EXP_COS && n_util_params != m) return fail(who, "neg_exp_cos needs m weights");
+  if (bocf_util_check(who, u, m, mode)) return -1;
   if (!Zf) return fail(who, "null Zf");
   if (Sf < 1 || Sf > 256) return fail(who, "Sf out of range (1 .. 256)");
   if (mode == BOCF_EU_MC && c->S_mc < 1) return fail(who, "no Monte-Carlo samples set (bocf_set_mc_samples)");
   if (mode == BOCF_EU_MC && c->S_mc > 256) return fail(who, "more than 256 Monte-Carlo samples");
   if (kg_ready(c, who)) return -1;
-  const int H = c->hyper_samples > 0 ? c->hyper_samples : 1;
-  const int Ha = (c->acq_hyper_samples > 0 && c->acq_hyper_samples < H) ? c->acq_hyper_samples : H;   // the convention of the other acquisitions
+  const int Ha = bocf_acq_hyper_count(c);                   // the convention of the other acquisitions
   mg = Ha * m;
   const int C = c->C, d = c->d, na = c->kg_na, nap = round_up(na, BOCF_TILE);
   const bool grad = dacq_out != nullptr;
@@ -226,23 +216,18 @@ extern "C" int bocf_acq_kg(bocf_ctx* c, int mode, int util_kind, const double* u
   }
   HIPCHK(hipSetDevice(c->device));
   // theta | prob | utility parameters | Zf in one upload
-  const size_t nth = (size_t)L * theta_dim, npar = nth + L + BOCF_MAX_M + (size_t)Sf * m;
-  std::vector<double> par(npar, 0.0);
-  memcpy(par.data(), theta, sizeof(double) * nth);
-  for (int l = 0; l < L; ++l) par[nth + l] = prob ? prob[l] : 1.0 / L;
-  for (int i = 0; i < n_util_params; ++i) par[nth + L + i] = util_params[i];
-  memcpy(par.data() + nth + L + BOCF_MAX_M, Zf, sizeof(double) * (size_t)Sf * m);
-  if (c->kg_par.ensure(sizeof(double) * npar) || c->kg_v0.ensure(sizeof(double) * (size_t)Ha * L) || c->acq.ensure(sizeof(double) * (size_t)round_up(C, BOCF_TILE)))
+  const UtilPack& pk = bocf_util_pack(u, Zf, (size_t)Sf * m, &c->util_up);
+  if (c->kg_par.ensure(pk.bytes()) || c->kg_v0.ensure(sizeof(double) * (size_t)Ha * L) || c->acq.ensure(sizeof(double) * (size_t)round_up(C, BOCF_TILE)))
     return -1;
   if (grad && (c->kg_dout.ensure(sizeof(double) * (size_t)C * d) || c->kg_astar.ensure(sizeof(int) * (size_t)C * L * Sf) ||
                c->kg_AB.ensure(sizeof(double) * (size_t)C * L * Sf * 2 * m)))
     return -1;
   c->have_acq = false;
-  HIPCHK(hipMemcpyAsync(c->kg_par.p, par.data(), sizeof(double) * npar, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->kg_par.p, pk.host.data(), pk.bytes(), hipMemcpyHostToDevice, c->stream));
   KgArgs a{};
   a.ldc = nap; a.lda = nap; a.nug = c->kg_nug.as<double>();
-  a.theta = c->kg_par.as<double>(); a.theta_dim = theta_dim; a.prob = a.theta + nth; a.L = L; a.util_params = a.prob + L;
-  a.Zf = a.util_params + BOCF_MAX_M; a.Sf = Sf;
+  a.theta = c->kg_par.as<double>() + pk.theta; a.theta_dim = theta_dim; a.prob = c->kg_par.as<double>() + pk.prob; a.L = L;
+  a.util_params = c->kg_par.as<double>() + pk.params; a.Zf = c->kg_par.as<double>() + pk.tail; a.Sf = Sf;
   a.Wt = mode == BOCF_EU_MC ? c->Wt.as<double>() : nullptr; a.S = mode == BOCF_EU_MC ? c->S_mc : 0;
   a.m = m; a.na = na; a.mode = mode; a.util_kind = util_kind; a.scale = 1.0 / Ha;
   for (int h = 0; h < Ha; ++h) {

@@ -192,12 +192,8 @@ extern "C" int bocf_path_utility(bocf_ctx* c, int util_kind, const double* util_
   if (per > BOCF_MAX_M) return fail(who, "more outputs per hyper-sample than the device utilities take (16)");
   if (util_kind == BOCF_UTIL_PROGRAM && bocf_check_resident_program(c, who, per, theta_dim, n_util_params)) return -1;
   HIPCHK(hipSetDevice(c->device));
-  // theta rows widened to at least m' columns (the utilities read theta[j] for j < m'), parameters to BOCF_MAX_M: zeros behind
-  const int tw = theta_dim > per ? theta_dim : (per > 1 ? per : 1);
-  std::vector<double> par((size_t)P * tw + BOCF_MAX_M, 0.0);
-  for (int p = 0; p < P; ++p)
-    for (int q = 0; q < theta_dim; ++q) par[(size_t)p * tw + q] = theta[(size_t)p * theta_dim + q];
-  for (int q = 0; q < n_util_params; ++q) par[(size_t)P * tw + q] = util_params[q];
+  std::vector<double> par;                                   // the widened theta rows | the parameters (util_args.h)
+  const int tw = bocf_util_pack_rows(theta, theta_dim, P, per, util_params, n_util_params, &par);
   const int* kids = BOCF_KIDS(c);
   std::vector<int> rows((size_t)C + c->m, 0);
   memcpy(rows.data(), row_path, sizeof(int) * (size_t)C);

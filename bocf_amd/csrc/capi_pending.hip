@@ -78,18 +78,13 @@ extern "C" int bocf_acq_pending(bocf_ctx* c, int util_kind, const double* util_p
                                 const double* prob, int L, double* acq_out, double* dacq_out) {
   static const char* who = "bocf_acq_pending";
   if (bocf_check_posterior(c, who)) return -1;
-  if (util_kind == BOCF_UTIL_PROGRAM)
-    return fail(who, "the pending-point acquisition does not take a utility program (BOCF_UTIL_PROGRAM): use one of the compiled-in utilities");
-  if (util_kind < BOCF_UTIL_LINEAR || util_kind > BOCF_UTIL_ROSENBROCK) return fail(who, "unknown utility kind");
+  const UtilArgs u{util_kind, util_params, n_util_params, theta, theta_dim, prob, L};
+  if (bocf_util_check_kind(who, u, "the pending-point acquisition does not take a utility program (BOCF_UTIL_PROGRAM): use one of the compiled-in utilities"))
+    return -1;
   int j0, mg, m;
   if (bocf_group_range(c, who, -1, &j0, &mg, &m)) return -1;
   if (m > BOCF_MAX_M) return fail(who, "more outputs per hyper-sample than the device utilities take (16)");
-  if (L < 1 || L > BOCF_MAX_L) return fail(who, "L out of range (1 .. 32)");
-  if (theta_dim < 1 || theta_dim > BOCF_MAX_M || !theta) return fail(who, "theta must be (L, 1 <= theta_dim <= 16)");
-  if ((util_kind == BOCF_UTIL_LINEAR || util_kind == BOCF_UTIL_NEG_SQ_DIST) && theta_dim != m) return fail(who, "theta_dim must equal m");
-  if (util_kind == BOCF_UTIL_ROSENBROCK && (m & 1)) return fail(who, "rosenbrock utility needs even m");
-  if (n_util_params < 0 || n_util_params > BOCF_MAX_M || (n_util_params > 0 && !util_params)) return fail(who, "bad utility parameters");
-  if (util_kind == BOCF_UTIL_NEG_EXP_COS && n_util_params != m) return fail(who, "neg_exp_cos needs m weights");
+  if (bocf_util_check(who, u, m, BOCF_EU_MC)) return -1;
   if (c->S_mc < 1) return fail(who, "no Monte-Carlo samples set (bocf_set_mc_samples)");
   if (c->S_mc > 256) return fail(who, "more than 256 Monte-Carlo samples");
   if (c->pd_r < 1) return fail(who, "no pending points: call bocf_set_pending_points after the fit");
@@ -97,8 +92,7 @@ extern "C" int bocf_acq_pending(bocf_ctx* c, int util_kind, const double* util_p
   if (c->C < 1) return fail(who, "no resident candidates (bocf_set_candidates)");
   if (c->d > BOCF_MAX_D) return fail(who, "input dimension too large");
   if (c->best_group >= c->m / m) return fail(who, "option best_group is not a valid hyper-sample index");
-  const int H = c->hyper_samples > 0 ? c->hyper_samples : 1;
-  const int Ha = (c->acq_hyper_samples > 0 && c->acq_hyper_samples < H) ? c->acq_hyper_samples : H;   // the convention of bocf_acq_kg
+  const int Ha = bocf_acq_hyper_count(c);
   mg = Ha * m;
   const int C = c->C, d = c->d, N = c->N, r = c->pd_r, S = c->pd_S, rp = BOCF_TILE;
   const bool grad = dacq_out != nullptr;
@@ -110,27 +104,24 @@ extern "C" int bocf_acq_pending(bocf_ctx* c, int util_kind, const double* util_p
   }
   HIPCHK(hipSetDevice(c->device));
   // theta | prob | utility parameters in one upload
-  const size_t nth = (size_t)L * theta_dim, npar = nth + L + BOCF_MAX_M;
-  std::vector<double> par(npar, 0.0);
-  memcpy(par.data(), theta, sizeof(double) * nth);
-  for (int l = 0; l < L; ++l) par[nth + l] = prob ? prob[l] : 1.0 / L;
-  for (int i = 0; i < n_util_params; ++i) par[nth + L + i] = util_params[i];
+  const UtilPack& pk = bocf_util_pack(u, nullptr, 0, &c->util_up);
   const int cap = round_up(C < chunk ? C : chunk, BOCF_TILE);
-  if (c->pd_par.ensure(sizeof(double) * npar) || c->pd_best.ensure(sizeof(double) * (size_t)Ha * L) || c->pd_T.ensure(sizeof(double) * (size_t)Ha * L * S) ||
+  if (c->pd_par.ensure(pk.bytes()) || c->pd_best.ensure(sizeof(double) * (size_t)Ha * L) || c->pd_T.ensure(sizeof(double) * (size_t)Ha * L * S) ||
       c->pd_muc.ensure(sizeof(double) * (size_t)mg * cap) || c->acq.ensure(sizeof(double) * (size_t)round_up(C, BOCF_TILE)))
     return -1;
   if (grad && (c->kg_dout.ensure(sizeof(double) * (size_t)C * d) || c->pd_E.ensure(sizeof(double) * (size_t)C * m * S))) return -1;
   c->have_acq = false;
-  HIPCHK(hipMemcpyAsync(c->pd_par.p, par.data(), sizeof(double) * npar, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->pd_par.p, pk.host.data(), pk.bytes(), hipMemcpyHostToDevice, c->stream));
   const size_t nQ = (size_t)c->m * r * r, nF = (size_t)c->m * r * S;
   const double* Qd = c->pd_QFG.as<double>();
   PendArgs a{};
-  a.ldc = rp; a.theta = c->pd_par.as<double>(); a.theta_dim = theta_dim; a.prob = a.theta + nth; a.L = L; a.util_params = a.prob + L;
+  a.ldc = rp; a.theta = c->pd_par.as<double>() + pk.theta; a.theta_dim = theta_dim; a.prob = c->pd_par.as<double>() + pk.prob; a.L = L;
+  a.util_params = c->pd_par.as<double>() + pk.params;
   a.Wt = c->Wt.as<double>(); a.m = m; a.r = r; a.S = S; a.util_kind = util_kind; a.scale = 1.0 / Ha; a.d = d;
   // thresholds: each hyper-sample's own best-so-far, or that of option best_group for all (the rule of the Monte-Carlo acquisitions),
   // into buffers of this path -- the acquisitions' best-so-far cache is left as it was
   for (int h = 0; h < Ha; ++h) {
-    const int gb = c->best_group >= 0 ? c->best_group : h;
+    const int gb = bocf_best_group_of(c, h);
     PendArgs t = a;
     t.F = Qd + nQ + (size_t)h * m * r * S;
     double* best = c->pd_best.as<double>() + (size_t)h * L;

@@ -241,18 +241,14 @@ extern "C" int bocf_thompson_select(bocf_ctx* c, int util_kind, const double* ut
   if (per > BOCF_MAX_M) return fail(who, "more outputs per hyper-sample than the device utilities take (16)");
   if (util_kind == BOCF_UTIL_PROGRAM && bocf_check_resident_program(c, who, per, theta_dim, n_util_params)) return -1;
   HIPCHK(hipSetDevice(c->device));
-  // theta rows widened to at least m' columns (the utilities read theta[j] for j < m'), parameters to BOCF_MAX_M: zeros behind
-  const int tw = theta_dim > per ? theta_dim : (per > 1 ? per : 1);
-  std::vector<double> th((size_t)P * tw, 0.0), pa(BOCF_MAX_M, 0.0);
-  for (int p = 0; p < P; ++p)
-    for (int q = 0; q < theta_dim; ++q) th[(size_t)p * tw + q] = theta[(size_t)p * theta_dim + q];
-  for (int q = 0; q < n_util_params; ++q) pa[q] = util_params[q];
+  std::vector<double> par;                                   // the widened theta rows | the parameters (util_args.h)
+  const int tw = bocf_util_pack_rows(theta, theta_dim, P, per, util_params, n_util_params, &par);
   const int nb = topk_num_blocks(C);
-  if (c->ts_theta.ensure(sizeof(double) * th.size()) || c->ts_params.ensure(sizeof(double) * BOCF_MAX_M) || c->ts_u.ensure(sizeof(double) * (size_t)P * C) ||
+  if (c->ts_theta.ensure(sizeof(double) * (size_t)P * tw) || c->ts_params.ensure(sizeof(double) * BOCF_MAX_M) || c->ts_u.ensure(sizeof(double) * (size_t)P * C) ||
       c->ts_mp.ensure(16 * (size_t)nb * k) || c->ts_out.ensure(16 * (size_t)P * k))
     return -1;
-  HIPCHK(hipMemcpyAsync(c->ts_theta.p, th.data(), sizeof(double) * th.size(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->ts_params.p, pa.data(), sizeof(double) * BOCF_MAX_M, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->ts_theta.p, par.data(), sizeof(double) * (size_t)P * tw, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->ts_params.p, par.data() + (size_t)P * tw, sizeof(double) * BOCF_MAX_M, hipMemcpyHostToDevice, c->stream));
   long long* oi = c->ts_out.as<long long>();
   double* ov = reinterpret_cast<double*>(oi + (size_t)P * k);
   long long* bi = c->ts_mp.as<long long>();

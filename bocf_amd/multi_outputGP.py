@@ -693,23 +693,17 @@ class multi_outputGP(object):
         select_topk (fetch=False returns None)."""
         mode = _ffi.eu_mode(mode)
         self._begin_acq(n_hyps, True)
-        if self._resident.reference is None or self._resident.reference[2] != self._fit_serial:
-            raise RuntimeError("no reference points resident for this fit: call set_reference_points")
-        if mode == _ffi.EU_MC:
-            if W is None:
-                raise ValueError("the Monte-Carlo mode needs W (S, output_dim)")
-            self.set_mc_samples(W)
-        n = self._set_candidates(np.atleast_2d(X))
-        Zf = _ffi.f64(np.atleast_2d(Zf))
-        if Zf.shape[1] != self.output_dim:
-            raise ValueError("Zf must be (Sf, output_dim)")
-        util = self._utility_args(util_params, thetas, prob)
-        acq = np.empty(n) if fetch else None
-        dacq = np.empty((n, self._X.shape[1])) if grad else None
-        if n:
-            _ffi.check(_ffi.load().bocf_acq_kg(self._context().handle, mode, int(util_kind), *util, _ffi.dptr(Zf), Zf.shape[0], _ffi.dptr(acq),
-                                               _ffi.dptr(dacq)), "bocf_acq_kg")
-        return (acq, dacq) if grad else acq
+        self._resident_for_fit("reference", "no reference points resident for this fit: call set_reference_points")
+        if mode == _ffi.EU_MC and W is None:
+            raise ValueError("the Monte-Carlo mode needs W (S, output_dim)")
+
+        def fantasies():
+            Z = _ffi.f64(np.atleast_2d(Zf))
+            if Z.shape[1] != self.output_dim:
+                raise ValueError("Zf must be (Sf, output_dim)")
+            return _ffi.dptr(Z), Z.shape[0]
+        return self._run_acq("bocf_acq_kg", (mode, int(util_kind)), X, util_params, thetas, prob, W if mode == _ffi.EU_MC else None, grad, fetch,
+                             tail=fantasies)
 
     # ---- pending points of a greedy batch -------------------------------------------------------------------------------------
     def set_pending_points(self, P, Zp, W=None):
@@ -739,9 +733,8 @@ class multi_outputGP(object):
 
     def pending_samples(self):
         """The joint samples F at the resident pending points, (H * output_dim, r, S) (bocf_get_pending_samples)."""
-        if self._resident.pending is None or self._resident.pending[4] != self._fit_serial:
-            raise RuntimeError("no pending points resident for this fit: call set_pending_points")
-        (r, _), (S, _, _) = self._resident.pending[0], self._resident.pending[2]
+        key = self._resident_for_fit("pending", "no pending points resident for this fit: call set_pending_points")
+        (r, _), (S, _, _) = key[0], key[2]
         F = np.empty((self.output_dim * self._H, r, S))
         _ffi.check(_ffi.load().bocf_get_pending_samples(self._context().handle, _ffi.dptr(F)), "bocf_get_pending_samples")
         return F
@@ -752,17 +745,8 @@ class multi_outputGP(object):
         acquisitions.  The best-so-far is that of acq_mc: the hyper-sample current on entry.  Returns alpha (n,), or
         (alpha (n,), d alpha / dX (n, d)) with grad=True.  The values stay on the device for select_topk (fetch=False returns None)."""
         self._begin_acq(n_hyps, False)
-        if self._resident.pending is None or self._resident.pending[4] != self._fit_serial:
-            raise RuntimeError("no pending points resident for this fit: call set_pending_points")
-        if W is not None:
-            self.set_mc_samples(W)
-        n = self._set_candidates(np.atleast_2d(X))
-        util = self._utility_args(util_params, thetas, prob)
-        acq = np.empty(n) if fetch else None
-        dacq = np.empty((n, self._X.shape[1])) if grad else None
-        if n:
-            _ffi.check(_ffi.load().bocf_acq_pending(self._context().handle, int(util_kind), *util, _ffi.dptr(acq), _ffi.dptr(dacq)), "bocf_acq_pending")
-        return (acq, dacq) if grad else acq
+        self._resident_for_fit("pending", "no pending points resident for this fit: call set_pending_points")
+        return self._run_acq("bocf_acq_pending", (int(util_kind),), X, util_params, thetas, prob, W, grad, fetch)
 
     # ---- linear output constraints and the constrained Monte-Carlo acquisition ---------------------------------------------------
     def set_output_constraints(self, constraints):
@@ -811,16 +795,7 @@ class multi_outputGP(object):
         device for select_topk (fetch=False returns None)."""
         self._begin_acq(n_hyps, False)
         self._constraints_resident()
-        if W is not None:
-            self.set_mc_samples(W)
-        n = self._set_candidates(np.atleast_2d(X))
-        util = self._utility_args(util_params, thetas, prob)
-        acq = np.empty(n) if fetch else None
-        dacq = np.empty((n, self._X.shape[1])) if grad else None
-        if n:
-            _ffi.check(_ffi.load().bocf_acq_mc_constrained(self._context().handle, int(util_kind), *util, _ffi.dptr(acq), _ffi.dptr(dacq)),
-                       "bocf_acq_mc_constrained")
-        return (acq, dacq) if grad else acq
+        return self._run_acq("bocf_acq_mc_constrained", (int(util_kind),), X, util_params, thetas, prob, W, grad, fetch)
 
     # ---- joint posterior and composite Thompson sampling ------------------------------------------------------------------------
     def _group(self):
@@ -879,10 +854,7 @@ class multi_outputGP(object):
         path_groups = np.asarray(path_groups, dtype=int)
         P = path_groups.size
         dev = path_groups if self._H > 1 else np.zeros(P, dtype=int)
-        kind = utility.device_kind(self.output_dim)
-        params = utility.device_params
-        if kind == _ffi.UTIL_PROGRAM:
-            self.set_utility_program(utility.program_blob)
+        kind, params = self._device_utility(utility)
         self._set_candidates(X)
         order = []
         for g in sorted(set(dev.tolist())):
@@ -890,7 +862,11 @@ class multi_outputGP(object):
             Zg = np.concatenate([Z[h] for h in hs], axis=2)
             self._posterior_samples(g, Zg, keep_out=False)
             order += [s for h in hs for s in np.flatnonzero(path_groups == h)]
-        order = np.asarray(order, dtype=int)
+        return self._select_paths(kind, params, thetas, np.asarray(order, dtype=int), k)
+
+    def _select_paths(self, kind, params, thetas, order, k):
+        """One bocf_thompson_select over the resident samples (the device's path p is path order[p]); arguments and result in path order."""
+        P = order.size
         pa, n_pa, th, tdim, _, _ = self._utility_args(params, thetas[order], None)
         idx = np.empty((P, k), dtype=np.int64)
         val = np.empty((P, k))
@@ -979,16 +955,14 @@ class multi_outputGP(object):
         rows = np.asarray(row_path, dtype=int).reshape(-1)
         if rows.size and (rows.min() < 0 or rows.max() >= rec["n"]):
             raise IndexError("row_path out of range (0 .. n_paths - 1)")
-        kind = utility.device_kind(self.output_dim)
-        if kind == _ffi.UTIL_PROGRAM:
-            self.set_utility_program(utility.program_blob)
+        kind, params = self._device_utility(utility)
         n = self._set_candidates(np.atleast_2d(X))
         if n != rows.size:
             raise ValueError("row_path must hold one path index per row of X")
         inv = np.empty(rec["n"], dtype=int)
         inv[rec["order"]] = np.arange(rec["n"])                 # path s -> the device's path number
         dev_rows = np.ascontiguousarray(inv[rows], dtype=np.int32)
-        pa, n_pa, th, tdim, _, _ = self._utility_args(utility.device_params, thetas[rec["order"]], None)
+        pa, n_pa, th, tdim, _, _ = self._utility_args(params, thetas[rec["order"]], None)
         val = np.empty(n)
         dval = np.empty((n, self._X.shape[1])) if grad else None
         if n:
@@ -1008,20 +982,10 @@ class multi_outputGP(object):
             raise ValueError("path_groups are not the hyper-samples the resident paths were drawn for (draw_paths)")
         P = rec["n"]
         thetas = _ffi.f64(np.asarray(thetas, dtype=float).reshape(P, -1))
-        kind = utility.device_kind(self.output_dim)
-        if kind == _ffi.UTIL_PROGRAM:
-            self.set_utility_program(utility.program_blob)
+        kind, params = self._device_utility(utility)
         self._set_candidates(X)
         self._path_values(rec, False)
-        order = rec["order"]
-        pa, n_pa, th, tdim, _, _ = self._utility_args(utility.device_params, thetas[order], None)
-        idx = np.empty((P, k), dtype=np.int64)
-        val = np.empty((P, k))
-        _ffi.check(_ffi.load().bocf_thompson_select(self._context().handle, kind, pa, n_pa, th, tdim, int(k), idx.ctypes.data_as(_ffi._c_ll_p),
-                                                    _ffi.dptr(val)), "bocf_thompson_select")
-        out_idx, out_val = np.empty_like(idx), np.empty_like(val)
-        out_idx[order], out_val[order] = idx, val
-        return out_idx, out_val
+        return self._select_paths(kind, params, thetas, rec["order"], k)
 
     def set_hyperparameters2(self, hyperparameters):
         """multi_outputGP.py:118-120: per-output hyper-sample indices; the device keeps hyper-samples aligned across
@@ -1109,6 +1073,35 @@ class multi_outputGP(object):
         prob = None if prob is None else _ffi.f64(np.atleast_1d(prob))
         return _ffi.dptr(params), 0 if params is None else params.size, _ffi.dptr(th), tdim, _ffi.dptr(prob), L
 
+    def _run_acq(self, name, head, X, util_params, thetas, prob, W, grad, fetch, tail=None):
+        """The tail the acquisition entry points share: W (S, output_dim) goes up when given, X (n, d) becomes the resident candidates,
+        then `name`(handle, *head, the utility block, *tail(), acq, dacq) runs unless n = 0 (`tail` checks and returns the arguments
+        behind the block).  Returns acq (n,) (None with fetch=False), or (acq, dacq (n, d)) with grad=True."""
+        if W is not None:
+            self.set_mc_samples(W)
+        n = self._set_candidates(np.atleast_2d(X))
+        extra = tail() if tail else ()
+        util = self._utility_args(util_params, thetas, prob)
+        acq = np.empty(n) if fetch else None
+        dacq = np.empty((n, self._X.shape[1])) if grad else None
+        if n:
+            _ffi.check(getattr(_ffi.load(), name)(self._context().handle, *head, *util, *extra, _ffi.dptr(acq), _ffi.dptr(dacq)), name)
+        return (acq, dacq) if grad else acq
+
+    def _device_utility(self, utility):
+        """(kind, params) of a Utility for the device; a utility program is staged."""
+        kind = utility.device_kind(self.output_dim)
+        if kind == _ffi.UTIL_PROGRAM:
+            self.set_utility_program(utility.program_blob)
+        return kind, utility.device_params
+
+    def _resident_for_fit(self, slot, message):
+        """The key of the resident `slot`, which ends in the serial of the fit it was staged for: the current one, or RuntimeError."""
+        key = getattr(self._resident, slot)
+        if key is None or key[-1] != self._fit_serial:
+            raise RuntimeError(message)
+        return key
+
     def _acq_linear(self, X, kind, thetas, prob, n_hyps, grad):
         self._begin_acq(n_hyps, True)
         n = self._set_candidates(np.atleast_2d(X))
@@ -1149,14 +1142,7 @@ class multi_outputGP(object):
         self._begin_acq(n_hyps, False)
         if util_kind == _ffi.UTIL_PROGRAM:
             self.set_utility_program(program)
-        if W is not None:
-            self.set_mc_samples(W)
-        n = self._set_candidates(np.atleast_2d(X))
-        util = self._utility_args(util_params, thetas, prob)
-        acq, dacq = np.empty(n), np.empty((n, self._X.shape[1]))
-        if n:
-            _ffi.check(_ffi.load().bocf_acq_mc_grad(self._context().handle, util_kind, *util, _ffi.dptr(acq), _ffi.dptr(dacq)), "bocf_acq_mc_grad")
-        return acq, dacq
+        return self._run_acq("bocf_acq_mc_grad", (util_kind,), X, util_params, thetas, prob, W, True, True)
 
     def set_mc_samples(self, W):
         self._ensure_fitted()

@@ -3,7 +3,8 @@ uploads are NOT repeated because the host knows the buffer is resident (W, Z, th
 the all-hyper-sample query caches).  `_ffi.load` is replaced by a recording stand-in, so no library and no GPU is needed.
 
 The expected trace, tests/golden/model_calls.json, was recorded with this module (`python tests/test_model_calls_cpu.py`) against the
-commit BEFORE the residency record / utility table refactor; it also holds one np.random.random() drawn after each scenario, which
+commit BEFORE the residency record / utility table refactor (the third scenario: against the commit before the model's acquisition
+tails were folded into _run_acq / _select_paths); it also holds one np.random.random() drawn after each scenario, which
 pins the number and the order of the global-RNG draws.  The stand-in leaves output arrays uninitialised: no scenario branches on a
 returned value.  Record again only when a change is MEANT to alter the calls."""
 import json
@@ -253,7 +254,79 @@ def scenario_hyper_samples(lib):
     model.posterior_mean(Xc)
 
 
-SCENARIOS = (("fixed", scenario_fixed), ("hyper_samples", scenario_hyper_samples))
+def scenario_batches_constraints_paths(lib):
+    """The pending-point, constrained and pathwise entry points, once with fixed hyper-parameters and once with H = 2 hyper-samples."""
+    from bocf_amd.constraints import OutputConstraints
+    rng = np.random.RandomState(5)
+    np.random.seed(6)
+    H = 2
+    X, Y = _data(rng)
+    Xc = rng.uniform(size=(C, D))
+    support, prob = rng.uniform(size=(L, M)), np.array([0.25, 0.25, 0.5])
+    fixed = B.multi_outputGP(M, fixed_hyps=True, noise_var=[1e-4] * M)
+    lib.mark("fixed hyper-parameters: updateModel")
+    fixed.updateModel(X, Y)
+    sampled = B.multi_outputGP(M, fixed_hyps=False, n_samples=H)
+    sampled._X, sampled._Y = np.ascontiguousarray(X), [y.copy() for y in Y]
+    sampled._kernel_ids = [_ffi.KERN_MATERN32, _ffi.KERN_SE]
+    sampled._instances = [[(1.0 + 0.1 * h, np.full(D, 0.5 - 0.05 * h), 1e-4) for _ in range(M)] for h in range(H)]
+    lib.mark("H = 2: fit")
+    sampled._fit()
+    U = B.Utility(parameter_dist=_dist(support, prob), device="neg_sq_dist")
+    U_prog = B.Utility(func=abs15, parameter_dist=_dist(support, prob), device="program")
+    cons = OutputConstraints([[1.0, -1.0], [0.5, 0.25]], [0.1, 0.2], eta=[1e-2, 1e-3])
+    for name, model in (("fixed", fixed), ("H = 2", sampled)):
+        W, W2 = rng.normal(size=(S, M)), rng.normal(size=(S, M))
+        P, Zp = rng.uniform(size=(2, D)), rng.normal(size=(S, M, 2))
+        lib.mark(name + ": pending points")
+        if model is sampled:
+            model.set_hyperparameters(1)
+        model.set_mc_samples(W)
+        model.set_pending_points(P, Zp)
+        model.set_pending_points(P, Zp)                       # resident: no call
+        model.set_pending_points(P[:1], Zp[:, :, :1], W=W2)   # W first, then the new set
+        model.pending_samples()
+        model.acq_pending(Xc, _ffi.UTIL_NEG_SQ_DIST, None, support, prob)
+        model.acq_pending(Xc[:1], _ffi.UTIL_NEG_SQ_DIST, None, support, prob, W=W2, n_hyps=1, grad=True)
+        model.acq_pending(Xc, _ffi.UTIL_NEG_EXP_COS, np.ones(M), support, None, W=W, fetch=False)
+        lib.mark(name + ": output constraints")
+        model.set_output_constraints(cons)
+        model.set_output_constraints(cons)                    # resident: no call
+        model.feasible_best(_ffi.UTIL_NEG_SQ_DIST, None, support)
+        model.acq_mc_constrained(Xc, _ffi.UTIL_NEG_SQ_DIST, None, support, prob)
+        model.acq_mc_constrained(Xc[:2], _ffi.UTIL_NEG_SUM_EXP, None, support[:, :1], None, W=W2, n_hyps=2, grad=True)
+        model.acq_mc_constrained(Xc, _ffi.UTIL_NEG_SQ_DIST, None, support, prob, fetch=False)
+        model.set_output_constraints(None)
+        try:
+            model.acq_mc_constrained(Xc, _ffi.UTIL_NEG_SQ_DIST, None, support, prob)
+            raise AssertionError("RuntimeError expected")
+        except RuntimeError:
+            pass
+        lib.mark(name + ": paths")
+        n_paths = 3
+        thetas = rng.uniform(size=(n_paths, M))
+        model.draw_paths(n_paths, n_features=4)
+        model.path_values(Xc)
+        model.path_utility(Xc, np.arange(C) % n_paths, thetas, U, grad=True)
+        model.path_utility(Xc[:2], [2, 0], thetas, U_prog)
+        model.pathwise_topk(Xc, thetas, model._path_groups(n_paths), U, 2)
+        model.pathwise_topk(Xc, thetas, model._path_groups(n_paths), U_prog, 2)
+        lib.mark(name + ": Monte-Carlo gradient with a utility program")
+        model.acq_mc_grad(Xc[:1], _ffi.UTIL_PROGRAM, None, support, prob, W=W, program=U_prog.program_blob)
+        model.acq_mc_grad(Xc[:2], _ffi.UTIL_PROGRAM, None, support, prob, n_hyps=1, program=U_prog.program_blob)
+        lib.mark(name + ": a new fit forgets the pending points and the paths")
+        model.updateModel(X, [y + 0.05 for y in Y]) if model is fixed else model._fit()
+        for call in (model.pending_samples, lambda: model.acq_pending(Xc, _ffi.UTIL_NEG_SQ_DIST, None, support, prob),
+                     lambda: model.path_values(Xc)):
+            try:
+                call()
+                raise AssertionError("RuntimeError expected")
+            except RuntimeError:
+                pass
+
+
+SCENARIOS = (("fixed", scenario_fixed), ("hyper_samples", scenario_hyper_samples),
+             ("batches_constraints_paths", scenario_batches_constraints_paths))
 
 
 def run(scenario, monkeypatch=None):
@@ -282,6 +355,10 @@ def test_calls_with_fixed_hyperparameters(monkeypatch):
 
 def test_calls_with_hyper_samples(monkeypatch):
     _check("hyper_samples", scenario_hyper_samples, monkeypatch)
+
+
+def test_calls_of_batches_constraints_and_paths(monkeypatch):
+    _check("batches_constraints_paths", scenario_batches_constraints_paths, monkeypatch)
 
 
 if __name__ == "__main__":
