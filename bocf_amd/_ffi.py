@@ -88,6 +88,11 @@ SIGNATURES = {
     "bocf_feasible_best": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int, _c_double_p, _c_ll_p]),
     "bocf_acq_mc_constrained": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int,
                                                _c_double_p, _c_double_p]),
+    "bocf_train_utility_range": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int, _c_double_p,
+                                                _c_double_p]),
+    "bocf_expected_utility_constrained": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int,
+                                                         _c_double_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int, _c_double_p, _c_double_p,
+                                                         _c_double_p]),
     "bocf_mean_at_train": (ctypes.c_int, [_ctx_p, _c_double_p]),
     "bocf_acq_linear_grad": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p]),
     "bocf_acq_mc_grad": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p,

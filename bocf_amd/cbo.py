@@ -209,10 +209,15 @@ class CBO(object):
     """cbo.py:19-58.  model: a bocf_amd.multi_outputGP; space: a Design_space; objective: a MultiObjective (or anything with
     evaluate / evaluate_w_noise returning (list of m (n, 1) arrays, cost)); acquisition: a bocf_amd acquisition (its `utility` is
     the loop's utility); evaluator: Sequential(acquisition); X_init (n, d); expectation_utility: the closed-form E[U] (psi) of the
-    recommendation step, or None (then the Monte-Carlo form, or the posterior mean for a linear utility)."""
+    recommendation step, or None (then the Monte-Carlo form, or the posterior mean for a linear utility).
+    constraints: an OutputConstraints makes the recommendation step feasibility-aware (opt-in; NOT picked up from the acquisition): the
+    recommended designs maximise the constrained expected utility (recommend.current_marginal_argmaxes), an infeasible outcome worth
+    infeasible_utility (a scalar or one value per utility parameter; default: the lowest utility of the posterior mean at the training
+    points), and a recommendation whose TRUE outputs violate constraints.feasible is scored with that worth in
+    historical_optimal_values.  last_recommendation carries pof, the smoothed probability of feasibility at the recommended points."""
 
     def __init__(self, model, space, objective, acquisition, evaluator, X_init, Y_init=None, cost=None, normalize_Y=False,
-                 model_update_interval=1, expectation_utility=None):
+                 model_update_interval=1, expectation_utility=None, constraints=None, infeasible_utility=None):
         if cost is not None:
             raise NotImplementedError("only a constant evaluation cost is supported (cost=None)")
         self.model = model
@@ -221,6 +226,9 @@ class CBO(object):
         self.acquisition = acquisition
         self.utility = acquisition.utility
         self.expectation_utility = expectation_utility
+        if constraints is None and infeasible_utility is not None:
+            raise ValueError("infeasible_utility is the worth of an outcome that violates `constraints`: give them")
+        self.constraints, self.infeasible_utility = constraints, infeasible_utility
         self.evaluator = evaluator
         self.X = X_init
         self.Y = Y_init
@@ -244,14 +252,22 @@ class CBO(object):
         """argmax_x sum_h E_n[U(theta_l, f(x))] for every parameter row, in one batch; current_argmax becomes the last one."""
         info = {}
         X, _ = current_marginal_argmaxes(self.model, self.space, self.utility, parameters, self.expectation_utility,
-                                         n_hyps=self.n_hyps_samples, n_starting=self.n_starting, n_anchor=self.n_anchor, info=info)
+                                         n_hyps=self.n_hyps_samples, n_starting=self.n_starting, n_anchor=self.n_anchor, info=info,
+                                         **self._constraint_arguments())
         self.last_recommendation = info
         self.current_argmax = np.atleast_2d(X[-1])
         return X
 
-    def _marginal_value(self, parameter, x):
-        """U(theta, f(x)) with the true (noiseless) objective at one recommended point."""
+    def _constraint_arguments(self):
+        """The two keywords of current_marginal_argmaxes; none without constraints, so that call is the one it always was."""
+        return {} if self.constraints is None else {"constraints": self.constraints, "infeasible_utility": self.infeasible_utility}
+
+    def _marginal_value(self, parameter, x, u_infeasible=None):
+        """U(theta, f(x)) with the true (noiseless) objective at one recommended point; with constraints, u_infeasible when the true
+        outputs there fail constraints.feasible."""
         fx = np.reshape(self.objective.evaluate(np.atleast_2d(x))[0], (self.n_attributes,))
+        if self.constraints is not None and u_infeasible is not None and not bool(self.constraints.feasible(fx)):
+            return u_infeasible
         return self.utility.eval_func(parameter, fx)
 
     def _parameters_of_this_step(self):
@@ -265,7 +281,8 @@ class CBO(object):
     def _score(self, parameters, weights):
         """sum_l w_l U(theta_l, f(x_l)) over the batched recommendations (a plain mean without weights), in parameter order."""
         X = self._recommend(parameters)
-        terms = [self._marginal_value(parameters[l], X[l]) for l in range(len(parameters))]
+        u0 = self.last_recommendation.get("u_infeasible") if self.constraints is not None else None
+        terms = [self._marginal_value(parameters[l], X[l], None if u0 is None else u0[l]) for l in range(len(parameters))]
         total = 0
         for l, t in enumerate(terms):
             total = total + (t * weights[l] if weights is not None else t)
@@ -285,7 +302,9 @@ class CBO(object):
         return self._score(self.utility.parameter_dist.sample(self.n_parameter_samples), None)
 
     def _current_marginal_max_value(self, parameter):
-        return self._marginal_value(parameter, self._current_marginal_argmax(parameter))
+        x = self._current_marginal_argmax(parameter)
+        u0 = self.last_recommendation.get("u_infeasible") if self.constraints is not None else None
+        return self._marginal_value(parameter, x, None if u0 is None else u0[0])
 
     def _current_marginal_argmax(self, parameter):
         """argmax_x sum_h E_n[U(theta, f(x))] for one parameter (the batched path with L = 1); sets current_argmax."""

@@ -210,6 +210,11 @@ struct bocf_ctx {
   // are left as they were
   int cq_K = 0, cq_m = 0;    // constraints resident (0 = none) and the outputs per hyper-sample they were given for
   DevBuf cq_tab, cq_par, cq_best, cq_nf;
+  // ---- constrained expected utility of the recommendation step (bocf_expected_utility_constrained, bocf_train_utility_range;
+  // capi_constrained.hip): parameters | u0 | rows of a call, its outputs and the utility range in buffers of their own -- the acquisition
+  // state, the incumbent buffers above and bocf_expected_utility's buffers are left as they were
+  DevBuf cu_par, cu_val, cu_pof, cu_grad, cu_rng;
+  std::vector<double> cu_tail;   // u0 (L) | row_param (C ints) as the tail of util_up's block (kept: its capacity is reused)
   UtilPack util_up;          // host source of the utility block's upload (util_args.h says why it lives here); kg_par, pd_par, cq_par are its device copies
 };
 
@@ -246,6 +251,8 @@ int bocf_enqueue_V(bocf_ctx* c, int j0, int mg, const double* Xq, int n, int npa
 // grad its input gradients) of every resident candidate, through the predict pass's plan and chunking; and two device vectors to the host
 // with ONE synchronisation (either may be empty)
 int bocf_acq_posterior(bocf_ctx* c, bool grad);
+// ... and the one bocf_expected_utility reads (predict_noiseless: no likelihood noise, clipped at 1e-10)
+int bocf_eu_posterior(bocf_ctx* c, bool grad);
 int bocf_copy_pair_out(bocf_ctx* c, const void* src0, double* out0, size_t b0, const void* src1, double* out1, size_t b1);
 
 

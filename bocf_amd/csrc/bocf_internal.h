@@ -510,3 +510,27 @@ void launch_feasible_best(const double* mu_train, int N, int m, int util_kind, c
                           const double* tab, int K, double* best, long long* nfeas, hipStream_t s);
 void launch_cacq(const CacqArgs& a, hipStream_t s);
 void launch_cacq_grad(const CacqArgs& a, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------
+// constrained expected utility of the recommendation step (ceu.hip): eu_kernel's Monte-Carlo form with every sample
+// weighed by phi and an infeasible outcome worth u0 -- G = sum_s [u0 + phi (U - u0)], P = mean_s phi
+// ---------------------------------------------------------------------------------------
+struct CeuArgs {
+  double* val; double* pof; double* grad;           // (C), (C), (C, d).  (First: with the outputs behind the inputs the compiler reserves a
+                                                    // 36-byte stack frame it never touches for ceu_kernel<2, true> and <3, true>)
+  const double* mean; const double* var; long ld;   // (m, ld) rows of one hyper-sample, first C columns valid
+  const double* dmean; const double* dvar; long ldg; int d;   // gradient form: (m, ldg, d)
+  int m, C, S, K;
+  int util_kind, theta_dim;
+  const double* theta; const double* u0;            // device (L, theta_dim), (L): the worth of an infeasible outcome per parameter
+  const int* rows;                                  // device (C): parameter index of every candidate, in [0, L)
+  const double* util_params;                        // (BOCF_MAX_M)
+  const double* Zt;                                 // (L, m, S) transposed normals of every parameter (bocf_set_eu_samples)
+  const double* tab;                                // A (K, m) | b (K) | 1 / eta (K)
+  int accumulate;                                   // written, or added to (hyper-sample h > 0)
+  double scale, pscale;                             // of G: n_hyps with one resident hyper-sample, else 1; of P: 1 / (n_h S)
+};
+void launch_ceu(const CeuArgs& a, bool grad, hipStream_t s);
+// min_out[l], max_out[l] = min / max over the N training points of U(theta_l, mu(X_i)): one workgroup per parameter, fixed order
+void launch_train_utility_range(const double* mu_train, int N, int m, int util_kind, const double* theta, int theta_dim, int L, const double* util_params,
+                                double* min_out, double* max_out, hipStream_t s);

@@ -114,7 +114,7 @@ extern "C" void bocf_destroy(bocf_ctx* c) {
                     &c->kg_par, &c->kg_v0, &c->kg_astar, &c->kg_AB, &c->kg_out, &c->kg_dout, &c->prog_buf,
                     &c->pd_XP, &c->pd_VP, &c->pd_Wp, &c->pd_muP, &c->pd_cov, &c->pd_pack, &c->pd_QFG, &c->pd_par, &c->pd_best, &c->pd_T, &c->pd_muc, &c->pd_E,
                     &c->pt_E, &c->pt_g, &c->pt_rhs, &c->pt_tmp, &c->pt_nug, &c->pt_par, &c->pt_rows, &c->pt_tab, &c->pt_pv, &c->pt_pg, &c->pt_val, &c->pt_grad,
-                    &c->cq_tab, &c->cq_par, &c->cq_best, &c->cq_nf};
+                    &c->cq_tab, &c->cq_par, &c->cq_best, &c->cq_nf, &c->cu_par, &c->cu_val, &c->cu_pof, &c->cu_grad, &c->cu_rng};
   for (DevBuf* b : bufs) b->release();
   if (c->infer_out) (void)hipHostFree(c->infer_out);
   if (c->tile_ctr) (void)hipFree(c->tile_ctr);
@@ -640,6 +640,7 @@ static int copy_pair_out(bocf_ctx* c, const void* src0, double* out0, size_t b0,
 }
 
 int bocf_acq_posterior(bocf_ctx* c, bool grad) { return run_predict(c, BOCF_ADD_NOISE | BOCF_CLIP, true, grad); }
+int bocf_eu_posterior(bocf_ctx* c, bool grad) { return run_predict(c, BOCF_CLIP, true, grad); }
 int bocf_copy_pair_out(bocf_ctx* c, const void* src0, double* out0, size_t b0, const void* src1, double* out1, size_t b1) {
   return copy_pair_out(c, src0, out0, b0, src1, out1, b1);
 }

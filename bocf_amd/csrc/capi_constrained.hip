@@ -5,7 +5,11 @@
 // acquisition vector for the selections.  The constraints do not depend on the factor: nothing here calls a drop function, and no fit,
 // data change or candidate upload forgets them.  The feasible incumbent is computed per call into buffers of this path (the
 // acquisitions' parameter and best-so-far caches are left as they were).  One stream, one synchronisation per call.
+// Below them the feasibility-aware recommendation step (kernels: ceu.hip): bocf_train_utility_range and
+// bocf_expected_utility_constrained -- bocf_expected_utility's Monte-Carlo form, posterior (no likelihood noise, clipped) and hyper-sample
+// rules with every sample weighed by the same phi; their argument checks are ceu_args.h's and run before the context is touched.
 #include "bocf_ctx.h"
+#include "ceu_args.h"
 
 #include <cmath>
 #include <cstring>
@@ -144,4 +148,78 @@ extern "C" int bocf_acq_mc_constrained(bocf_ctx* c, int util_kind, const double*
   c->have_acq = true;
   const size_t b0 = acq_out ? sizeof(double) * (size_t)c->C : 0, b1 = grad ? sizeof(double) * (size_t)c->C * c->d : 0;
   return bocf_copy_pair_out(c, c->acq.p, acq_out, b0, c->dacq.p, dacq_out, b1);
+}
+
+// ---- the feasibility-aware recommendation step ------------------------------------------------------------------------------------------
+static CeuState ceu_state(const bocf_ctx* c) {
+  if (!c) return CeuState{};
+  return CeuState{c->fitted, c->canned, c->m, c->hyper_samples, c->best_group, c->cq_K, c->cq_m, c->eu_S, c->eu_L, c->eu_m, c->d, c->C};
+}
+
+extern "C" int bocf_train_utility_range(bocf_ctx* c, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim, int L,
+                                        double* min_out, double* max_out) {
+  static const char* who = "bocf_train_utility_range";
+  const UtilArgs u{util_kind, util_params, n_util_params, theta, theta_dim, nullptr, L};
+  const int m = bocf_ceu_check_utility(who, ceu_state(c), u, false);
+  if (m < 0) return -1;
+  if (!min_out || !max_out) return fail(who, "null min_out / max_out");
+  HIPCHK(hipSetDevice(c->device));
+  const UtilPack& pk = bocf_util_pack(u, nullptr, 0, &c->util_up);
+  if (c->cu_par.ensure(pk.bytes()) || c->cu_rng.ensure(sizeof(double) * 2 * (size_t)L)) return -1;
+  HIPCHK(hipMemcpyAsync(c->cu_par.p, pk.host.data(), pk.bytes(), hipMemcpyHostToDevice, c->stream));
+  const double* par = c->cu_par.as<double>();
+  double* rng = c->cu_rng.as<double>();
+  const int gb = bocf_best_group_of(c, 0);
+  launch_train_utility_range(c->mu_train.as<double>() + (size_t)gb * m * c->N, c->N, m, util_kind, par + pk.theta, theta_dim, L, par + pk.params, rng, rng + L,
+                             c->stream);
+  return bocf_copy_pair_out(c, rng, min_out, sizeof(double) * L, rng + L, max_out, sizeof(double) * L);
+}
+
+extern "C" int bocf_expected_utility_constrained(bocf_ctx* c, int util_kind, const double* util_params, int n_util_params, const double* theta,
+                                                 int theta_dim, int L, const double* u_infeasible, const int* row_param, int n_hyps, double* val_out,
+                                                 double* pof_out, double* grad_out) {
+  static const char* who = "bocf_expected_utility_constrained";
+  const UtilArgs u{util_kind, util_params, n_util_params, theta, theta_dim, nullptr, L};
+  const CeuState st = ceu_state(c);
+  const int m = bocf_ceu_check_utility(who, st, u, true);
+  if (m < 0) return -1;
+  const bool grad = grad_out != nullptr;
+  const int rc = bocf_ceu_check_call(who, st, u, m, u_infeasible, row_param, n_hyps, val_out, grad);
+  if (rc) return rc < 0 ? -1 : 0;
+  HIPCHK(hipSetDevice(c->device));
+  const int C = c->C, d = c->d;
+  // theta | prob | utility parameters | u0 (L) | rows (C ints) in one block, one upload
+  const size_t nrow = ((size_t)C + 1) / 2;
+  c->cu_tail.assign((size_t)L + nrow, 0.0);
+  memcpy(c->cu_tail.data(), u_infeasible, sizeof(double) * L);
+  memcpy(c->cu_tail.data() + L, row_param, sizeof(int) * (size_t)C);
+  const UtilPack& pk = bocf_util_pack(u, c->cu_tail.data(), c->cu_tail.size(), &c->util_up);
+  if (c->cu_par.ensure(pk.bytes()) || c->cu_val.ensure(sizeof(double) * (size_t)C) || c->cu_pof.ensure(sizeof(double) * (size_t)C) ||
+      (grad && c->cu_grad.ensure(sizeof(double) * (size_t)C * d)))
+    return -1;
+  HIPCHK(hipMemcpyAsync(c->cu_par.p, pk.host.data(), pk.bytes(), hipMemcpyHostToDevice, c->stream));
+  if (bocf_eu_posterior(c, grad)) return -1;
+  const double* par = c->cu_par.as<double>();
+  const int H = c->hyper_samples;
+  const int nh = H == 1 ? 1 : n_hyps;             // the hyper-sample rules of bocf_expected_utility
+  CeuArgs a{};
+  a.val = c->cu_val.as<double>(); a.pof = c->cu_pof.as<double>(); a.grad = grad ? c->cu_grad.as<double>() : nullptr;
+  a.ld = c->pred_cap; a.ldg = c->pred_cap; a.d = d;
+  a.m = m; a.C = C; a.S = c->eu_S; a.K = c->cq_K; a.util_kind = util_kind; a.theta_dim = theta_dim;
+  a.theta = par + pk.theta; a.util_params = par + pk.params; a.u0 = par + pk.tail;
+  a.rows = reinterpret_cast<const int*>(par + pk.tail + L);
+  a.Zt = c->eu_Z.as<double>(); a.tab = c->cq_tab.as<double>();
+  a.scale = H == 1 ? (double)n_hyps : 1.0;
+  a.pscale = 1.0 / ((double)nh * (double)c->eu_S);
+  for (int h = 0; h < nh; ++h) {
+    a.mean = c->mean.as<double>() + (size_t)h * m * a.ld;
+    a.var = c->var.as<double>() + (size_t)h * m * a.ld;
+    if (grad) { a.dmean = c->dmean.as<double>() + (size_t)h * m * a.ldg * d; a.dvar = c->dvar.as<double>() + (size_t)h * m * a.ldg * d; }
+    a.accumulate = h > 0;
+    PhaseTimer t(c, "ceu");
+    launch_ceu(a, grad, c->stream);
+  }
+  // the feasibility is enqueued behind the kernels; the pair's one synchronisation covers it
+  if (pof_out) HIPCHK(hipMemcpyAsync(pof_out, c->cu_pof.p, sizeof(double) * (size_t)C, hipMemcpyDeviceToHost, c->stream));
+  return bocf_copy_pair_out(c, c->cu_val.p, val_out, sizeof(double) * (size_t)C, c->cu_grad.p, grad_out, grad ? sizeof(double) * (size_t)C * d : 0);
 }

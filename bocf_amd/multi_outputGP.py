@@ -1248,6 +1248,78 @@ class multi_outputGP(object):
             self._current_h = min(n_h, self._H) - 1
         return (val, dval) if grad else val
 
+    # ---- feasibility-aware recommendation: the constrained expected utility -----------------------------------
+    def _device_kind(self, utility):
+        """(kind, device params or None) of a Utility with a device kind, a device utility name or its _ffi.UTIL_* value."""
+        if hasattr(utility, "device_kind"):
+            return utility.device_kind(self.output_dim), utility.device_params
+        if isinstance(utility, str):
+            return device_utility(utility).kind, None
+        return int(utility), None
+
+    def train_utility_range(self, kind, util_params, thetas):
+        """(min (L,), max (L,)) of U(theta_l, mu(X_i)) over all training points (bocf_train_utility_range); the posterior mean is that of
+        the current hyper-sample.  `kind`: as `utility` in expected_utility_constrained.  The min is the recommendation step's default
+        worth of an infeasible outcome."""
+        self._ensure_fitted()
+        if not self.fixed_hyps:
+            self._context().set_option("best_group", self._current_h)
+        kind, own = self._device_kind(kind)
+        params, n_params, th, tdim, _, L = self._utility_args(own if util_params is None else util_params, thetas, None)
+        lo, hi = np.empty(L), np.empty(L)
+        _ffi.check(_ffi.load().bocf_train_utility_range(self._context().handle, kind, params, n_params, th, tdim, L, _ffi.dptr(lo), _ffi.dptr(hi)),
+                   "bocf_train_utility_range")
+        return lo, hi
+
+    def expected_utility_constrained(self, X, utility, thetas, row_param, u_infeasible, Z, n_hyps=None, grad=False, util_params=None):
+        """The constrained expected utility of the recommendation step on the device (bocf_expected_utility_constrained), all utility
+        parameters in one call: row i of X takes parameter thetas[row_param[i]], its normals Z[row_param[i]] and the worth
+        u_infeasible[row_param[i]] of an infeasible outcome, and gets
+
+            v_i   = sum_{h < n_hyps} sum_s [ u0 + phi(y_s) (U(theta, y_s) - u0) ],   y_s = mu_h + sigma_h o Z_s      (a sum, as expected_utility's)
+            pof_i = mean over h and s of phi(y_s)                                     (smoothed probability of feasibility)
+
+        under the noiseless posterior, phi from the resident constraints (set_output_constraints).  `utility`: a Utility with a compiled-in
+        device kind, a device utility name or its _ffi.UTIL_* value (a utility program is refused); u_infeasible: a scalar or (L,); Z
+        (L, S, m).  X = None, n_hyps and the hyper-sample the model is left on: as in expected_utility.  Returns (v (n,), pof (n,)), or
+        (v, pof, dv/dX (n, d)) with grad=True; pof has no gradient."""
+        self._ensure_fitted()
+        self._constraints_resident()
+        kind, own = self._device_kind(utility)
+        if util_params is None:
+            util_params = own
+        n_h = min(10, self.number_of_hyps_samples()) if n_hyps is None else int(n_hyps)
+        if n_h < 1:
+            raise ValueError("n_hyps must be >= 1")
+        if not self.fixed_hyps and n_h > self._H:
+            raise IndexError("n_hyps = %d exceeds the %d resident hyper-samples" % (n_h, self._H))
+        th = _ffi.f64(thetas)
+        if th.ndim != 2:
+            raise ValueError("thetas must be 2-D (L, theta_dim); write L scalar parameters as an (L, 1) array")
+        u0 = _ffi.f64(np.broadcast_to(np.asarray(u_infeasible, dtype=float), (th.shape[0],)))
+        rows = np.ascontiguousarray(np.asarray(row_param).reshape(-1), dtype=np.int32)
+        if Z is None:
+            raise ValueError("the constrained expected utility needs Z (L, S, output_dim)")
+        self.set_eu_samples(Z)
+        if X is not None:
+            n = self._set_candidates(np.atleast_2d(X))
+            if n != rows.size:
+                raise ValueError("row_param must hold one parameter index per row of X")
+        elif self._resident.candidates is None or self._resident.candidates != rows.size:
+            raise ValueError("X = None evaluates the resident candidates (%s): row_param must hold one index per candidate, it holds %d"
+                             % ("none known" if self._resident.candidates is None else self._resident.candidates, rows.size))
+        n = rows.size
+        params, n_params, th, tdim, _, L = self._utility_args(util_params, th, None)
+        val, pof = np.empty(n), np.empty(n)
+        dval = np.empty((n, self._X.shape[1])) if grad else None
+        if n:
+            _ffi.check(_ffi.load().bocf_expected_utility_constrained(self._context().handle, kind, params, n_params, th, tdim, L, _ffi.dptr(u0),
+                                                                     rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), n_h, _ffi.dptr(val),
+                                                                     _ffi.dptr(pof), _ffi.dptr(dval)), "bocf_expected_utility_constrained")
+        if not self.fixed_hyps:
+            self._current_h = min(n_h, self._H) - 1
+        return (val, pof, dval) if grad else (val, pof)
+
     def select_topk(self, k):
         """(indices, values) of the k best candidates of the last acquisition call -- the
         np.argsort(-acq)[:k] of anchor_points_generator.py:61, ties to the lowest index.  A NaN

@@ -41,13 +41,14 @@ def branch_of(utility, expectation_utility=None):
     return "mc"
 
 
-def draw_inputs(space, branch, n_parameters, m, n_starting=200):
+def draw_inputs(space, branch, n_parameters, m, n_starting=200, always_Z=False):
     """The random numbers of one _current_max_value after its parameter draw, in the reference's order: per parameter, Z (50, m)
-    (Monte-Carlo branch only) then the (n_starting, d) random design.  Returns (Z (L, 50, m) or None, designs (L, n_starting, d))."""
+    (Monte-Carlo branch only; with always_Z -- the constrained step, which has the Monte-Carlo form only -- in every branch) then the
+    (n_starting, d) random design.  Returns (Z (L, 50, m) or None, designs (L, n_starting, d))."""
     bounds = _bounds_of(space)
     Zs, designs = [], []
     for _ in range(n_parameters):
-        if branch == "mc":
+        if branch == "mc" or always_Z:
             Zs.append(np.random.normal(size=(N_Z_SAMPLES, m)))
         designs.append(samples_multidimensional_uniform(bounds, n_starting))
     return (np.stack(Zs) if Zs else None), np.stack(designs)
@@ -199,26 +200,72 @@ def optimize_batched(evaluator, designs, bounds, n_anchor=24, info=None):
     return x_best, -f_best
 
 
+def constrained_device_evaluator(model, utility, parameters, Z, u_infeasible, n_hyps=None):
+    """ev(X, rows, grad) -> (G (n,), dG/dX (n, d) or None) from bocf_expected_utility_constrained (the constraints are resident on the
+    model), and ev.pof(X, rows) -> the smoothed probability of feasibility (n,).  The utility's compiled-in device kind in every branch
+    (the linear kind for a linear utility); a utility without one raises NotImplementedError: this path has no host loop."""
+    m = model.output_dim
+    kind = _ffi.UTIL_LINEAR if utility.linear else utility.device_kind(m)
+    if kind == _ffi.UTIL_PROGRAM:
+        raise NotImplementedError("the constrained recommendation step takes the compiled-in device utilities only, not a utility program")
+    thetas = np.asarray(parameters, dtype=float).reshape(len(parameters), -1)
+
+    def ev(X, rows, grad=False):
+        out = model.expected_utility_constrained(X, kind, thetas, rows, u_infeasible, Z, n_hyps=n_hyps, grad=grad, util_params=utility.device_params)
+        return (out[0], out[2]) if grad else (out[0], None)
+    ev.pof = lambda X, rows: model.expected_utility_constrained(X, kind, thetas, rows, u_infeasible, Z, n_hyps=n_hyps,
+                                                                util_params=utility.device_params)[1]
+    return ev
+
+
 def current_marginal_argmaxes(model, space, utility, parameters, expectation_utility=None, n_hyps=None, n_starting=200, n_anchor=24,
-                              evaluator=None, info=None):
+                              evaluator=None, info=None, constraints=None, infeasible_utility=None):
     """x_l = argmax_x sum_{h < n_hyps} E_n[U(theta_l, f(x))] for every row theta_l of `parameters`, all in one batch (what
     cbo.py:121-235 computes for one parameter).  Draws Z and the random designs first (see the module docstring), then
     scores, refines and selects on the device.  n_hyps defaults to min(10, model.number_of_hyps_samples()) (cbo.py:52).
     `evaluator(parameters, Z)`, if given, builds the objective in place of the model's: it returns a callable ev(X, rows, grad) ->
     (sum_h E_h[U(theta_{rows[i]}, f(X_i))] (n,), its gradient (n, d) or None) -- e.g. a CPU restatement; Z is None outside the
     Monte-Carlo branch.  By default the device evaluates it, or the host loops when the utility / psi is outside the device's
-    closed set.  Returns (x (L, d), values (L,)); `info`, if a dict, receives Z, the designs, the anchors and the L-BFGS counters."""
+    closed set.  Returns (x (L, d), values (L,)); `info`, if a dict, receives Z, the designs, the anchors and the L-BFGS counters.
+
+    constraints: an OutputConstraints makes the step feasibility-aware: the objective becomes the constrained
+    expected utility  sum_h sum_s [u0_l + phi(y_s) (U(theta_l, y_s) - u0_l)], an infeasible outcome worth u0_l = infeasible_utility (a
+    scalar or (L,); default: the min of U(theta_l, mu(X_i)) over the training points, model.train_utility_range).  The constraints are
+    staged on the model (free when already resident).  There is no mean or closed form once phi multiplies the utility: every branch
+    takes the Monte-Carlo form, so Z is drawn in every branch, in the Monte-Carlo branch's order -- the draws from np.random differ from
+    the unconstrained call's only then.  `evaluator(parameters, Z, constraints, u_infeasible)` then takes two more arguments, and its
+    callable may carry ev.pof(X, rows).  `info` additionally receives pof (L,) at the returned points and u_infeasible (L,)."""
     parameters = np.asarray(parameters, dtype=float)
     if parameters.ndim == 1:
         parameters = parameters[:, None]
     L, m = len(parameters), model.output_dim
     n_h = min(10, model.number_of_hyps_samples()) if n_hyps is None else int(n_hyps)
     branch = branch_of(utility, expectation_utility)
-    Z, designs = draw_inputs(space, branch, L, m, n_starting)
-    ev = make_evaluator(model, branch, utility, parameters, expectation_utility, Z, n_h) if evaluator is None else evaluator(parameters, Z)
+    if constraints is None:
+        if infeasible_utility is not None:
+            raise ValueError("infeasible_utility is the worth of an outcome that violates `constraints`: give them")
+        Z, designs = draw_inputs(space, branch, L, m, n_starting)
+        ev = make_evaluator(model, branch, utility, parameters, expectation_utility, Z, n_h) if evaluator is None else evaluator(parameters, Z)
+        if info is not None:
+            info.update(Z=Z, designs=designs, branch=branch)
+        return optimize_batched(ev, designs, _bounds_of(space), n_anchor, info)
+    Z, designs = draw_inputs(space, branch, L, m, n_starting, always_Z=True)
+    if evaluator is None:
+        model.set_output_constraints(constraints)
+    if infeasible_utility is None:
+        kind = _ffi.UTIL_LINEAR if utility.linear else utility.device_kind(m)
+        u0 = np.asarray(model.train_utility_range(kind, utility.device_params, parameters)[0], dtype=float)
+    else:
+        u0 = np.array(np.broadcast_to(np.asarray(infeasible_utility, dtype=float), (L,)))
+    if not np.all(np.isfinite(u0)):
+        raise ValueError("infeasible_utility must be finite")
+    ev = constrained_device_evaluator(model, utility, parameters, Z, u0, n_h) if evaluator is None else evaluator(parameters, Z, constraints, u0)
     if info is not None:
         info.update(Z=Z, designs=designs, branch=branch)
-    return optimize_batched(ev, designs, _bounds_of(space), n_anchor, info)
+    X, values = optimize_batched(ev, designs, _bounds_of(space), n_anchor, info)
+    if info is not None:
+        info.update(u_infeasible=u0, pof=np.asarray(ev.pof(X, np.arange(L)), dtype=float) if hasattr(ev, "pof") else None)
+    return X, values
 
 
 def make_evaluator(model, branch, utility, parameters, expectation_utility=None, Z=None, n_hyps=None):

@@ -524,6 +524,36 @@ int bocf_feasible_best(bocf_ctx* ctx, int util_kind, const double* util_params, 
 int bocf_acq_mc_constrained(bocf_ctx* ctx, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim,
                             const double* prob, int L, double* acq_out, double* dacq_out);
 
+/* ---- feasibility-aware recommendation: the constrained expected utility.  bocf_expected_utility in its Monte-Carlo
+ * form with every sample weighed by the phi above (the resident set of bocf_set_output_constraints) and an infeasible outcome worth a
+ * constant u0_l per utility parameter.  Per hyper-sample, with the posterior of bocf_expected_utility (predict_noiseless: NO likelihood
+ * noise, variance clipped at 1e-10 -- not the noisy one of bocf_acq_mc) and Z the parameter's own normals of bocf_set_eu_samples:
+ *   y_s(x)  = mu(x) + sigma(x) o Z_s                     Z block row_param[c]
+ *   T_s     = phi(y_s) (U(theta_l, y_s) - u0_l)
+ *   G_l(x)  = sum_{h < n_hyps} sum_{s < S} [ u0_l + T_s ]        a SUM, as bocf_expected_utility's; one resident hyper-sample counts n_hyps times
+ *   P(x)    = (1 / (n_h S)) sum_h sum_s phi(y_s)                 smoothed probability of feasibility, a MEAN (n_h = hyper-samples visited)
+ *   dT/dy_j = phi (dU/dy_j - (U - u0_l) q_j),   q_j = sum_k (1 - s_k) A_kj / eta_k     (1 - s_k from the same e as s_k, never a difference)
+ *   A_j = sum_s dT/dy_j,  B_j = sum_s dT/dy_j Z_sj / (2 sigma_j),  dG/dx_q = sum_h sum_j A_j dmu_j/dx_q + B_j dsigma^2_j/dx_q.
+ * Vacuous constraints give phi = 1 exactly: G is then bocf_expected_utility's BOCF_EU_MC value (up to the order of the sums) and P = 1.  u0
+ * enters through U - u0 only: G is affine in u0 with slope sum (1 - phi).  Once phi multiplies the utility there is no mean or closed
+ * form: every branch of the recommendation step takes this Monte-Carlo form with the utility's compiled-in kind (BOCF_UTIL_LINEAR for the
+ * linear branch); BOCF_UTIL_PROGRAM is refused.  P is value-only.  fp64; every failure returns < 0 with the entry point's name in the
+ * error text; the argument checks need no device and run before the context is touched.
+ *
+ * bocf_train_utility_range: min_out (L), max_out (L) = the range of U(theta_l, mu_g(X_i)) over all N training points, g the hyper-sample of
+ *   option best_group (-1: hyper-sample 0) -- the default u0 is the min.  Needs no constraints.
+ * bocf_expected_utility_constrained: candidate c takes parameter row_param[c] in [0, L) of theta (L, theta_dim) and u_infeasible (L, every
+ *   entry finite); val_out (C) = G, pof_out (C) = P or NULL, grad_out (C, d) = dG/dx or NULL (value only).  The hyper-sample rules are
+ *   bocf_expected_utility's (the first n_hyps of H are summed; H = 1 is scaled by n_hyps; more than are resident is refused).  The value
+ *   form also runs on a bocf_set_posterior context; the gradient form refuses it, and d > 64.  Writes buffers of its own: the acquisition
+ *   vector, the samples of bocf_set_mc_samples, the parameter and best-so-far caches, the incumbent buffers of bocf_acq_mc_constrained
+ *   and bocf_expected_utility's buffers are left as they were.  One stream, one synchronisation. */
+int bocf_train_utility_range(bocf_ctx* ctx, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim,
+                             int L, double* min_out, double* max_out);
+int bocf_expected_utility_constrained(bocf_ctx* ctx, int util_kind, const double* util_params, int n_util_params, const double* theta,
+                                      int theta_dim, int L, const double* u_infeasible, const int* row_param, int n_hyps, double* val_out,
+                                      double* pof_out, double* grad_out);
+
 /* ---- multi-GPU: candidate shards, ONE collective.  One process per GPU, one context per process.  The
  * reference's own candidate parallelism is a pathos process pool over single candidates (uEI_noiseless.py:85-97); here rank
  * r scores the contiguous slice [lo_r, hi_r) of the batch against its resident fit and the ranks exchange only their k
