@@ -48,8 +48,14 @@ __device__ __forceinline__ void dd_add_acc(double& s, double& c, double hi, doub
 // by rint(x log2 e) with a two-part ln 2, degree-11 polynomial, ldexp) WITHOUT its two range selects (x > 1024 -> inf, x < -1075 -> 0):
 // every covariance function of the path takes exp of -r^2/2, -sqrt(5) r or -sqrt(3) r.  Same operations on the same operands: the same bits
 // as exp() on 2^30 arguments across [-745.2, 0] (tools/hbm_kernel_probe.hip) and 0 below -1075; 5 of the ~56 vector instructions per element
-// of the K builds.
-__device__ __forceinline__ double bocf_exp_nonpos(double x) {
+// of the K builds.  tests/test_gpu_extremes.py (test_ramp_train_kernel_through_the_subnormal_band) walks the K builds through the normal
+// range, the subnormal band, true zero and the clamp against a long-double truth, entry by entry.
+//
+// bocf_exp_nonpos_times(x, a) = a exp(x) with ONE rounding into the subnormal range: the amplitude goes into the ldexp, a * ldexp(p, n)
+// -> ldexp(a * p, n).  Wherever exp(x) is a normal number the two are the same bits (a power of two commutes with the rounding of the
+// product); below, exp(x) alone keeps 52 - (-1022 - n) bits and a Matern amplitude (1 + u + 5/3 r2 ~ 1.9e5 at u = 745) multiplied that
+// rounding error up: 9.1e4 subnormal ulps in K at l = 1e-3 (Matern52), 367 (Matern32), against <= 1 now.
+__device__ __forceinline__ double bocf_exp_nonpos_times(double x, double a) {
   x = __builtin_fmax(x, -1100.0);                        // (far-apart points with tiny lengthscales: below -1075 the library returns 0, and so does ldexp here)
   const double dn = __builtin_rint(x * 0x1.71547652b82fep+0);
   const double t = __builtin_fma(-dn, 0x1.abc9e3b39803fp-56, __builtin_fma(-dn, 0x1.62e42fefa39efp-1, x));
@@ -64,8 +70,9 @@ __device__ __forceinline__ double bocf_exp_nonpos(double x) {
   p = __builtin_fma(t, p, 0x1.000000000000bp-1);
   p = __builtin_fma(t, p, 1.0);
   p = __builtin_fma(t, p, 1.0);
-  return __builtin_ldexp(p, (int)dn);
+  return __builtin_ldexp(a * p, (int)dn);
 }
+__device__ __forceinline__ double bocf_exp_nonpos(double x) { return bocf_exp_nonpos_times(x, 1.0); }      // (1.0 * p is p: the same instructions as before)
 
 // ---------------------------------------------------------------------------------------
 // f64 MFMA GEMM (gemm_f64.hip):  C[r][c] = beta*Cin[r][c] + alpha * sum_kk A[kk][r] * B[kk][c]

@@ -15,7 +15,10 @@
 // Both are an amplitude times the same exponential, k = A_k e^{-u} and f = A_f e^{-u}, and the pieces below are u, A_k and A_f, keyed by
 // the compile-time family FAM in {0, 2, 3}.  A caller that needs both k and f, or keeps the exponential for later, takes
 // u = kern_decay<FAM>(r2) and e = bocf_exp_nonpos(-u) once and multiplies the amplitudes by e itself; everybody else calls the two
-// wrappers at the end, which take the runtime (or template-constant) kernel id.
+// wrappers at the end, which take the runtime (or template-constant) kernel id.  The wrappers hand the amplitude to the exponential's
+// final ldexp (bocf_exp_nonpos_times): the same bits as A * e wherever e is a normal number (u < 708.39), and one rounding instead of an
+// amplified one where e is subnormal -- the K builds hold |K - K_true| <= one subnormal ulp there (tests/test_gpu_extremes.py).  A caller
+// that keeps e sums its products, and a term of 1e-317 with 367 or 9e4 ulps of error leaves no trace in a sum.
 #pragma once
 #include "bocf_internal.h"
 
@@ -54,12 +57,12 @@ __device__ __forceinline__ double kern_f_amp(double variance, double u) {
 template <int FAM>
 __device__ __forceinline__ double kern_of_r2_family(double variance, double r2) {
   const double u = kern_decay<FAM>(r2);
-  return kern_value_amp<FAM>(variance, r2, u) * bocf_exp_nonpos(-u);
+  return bocf_exp_nonpos_times(-u, kern_value_amp<FAM>(variance, r2, u));      // (A_k e^{-u}, rounded once where e^{-u} is subnormal)
 }
 template <int FAM>
 __device__ __forceinline__ double kern_dfac_family(double variance, double r2) {
   const double u = kern_decay<FAM>(r2);
-  return kern_f_amp<FAM>(-variance, u) * bocf_exp_nonpos(-u);      // (-f: A_f is linear in the variance, the sign rides on it -- exact)
+  return bocf_exp_nonpos_times(-u, kern_f_amp<FAM>(-variance, u));   // (-f: A_f is linear in the variance, the sign rides on it -- exact)
 }
 
 // k(r) and -f(r) by kernel id (ids 0 and 1 are family 0): a template constant in the family-templated kernels, the launch's runtime id in

@@ -24,7 +24,7 @@ __device__ __forceinline__ void path_sincos(double x, double* sn, double* cs) { 
 // out[j][c][s] = (ymean_j) + sum_{i < N} k_j(x_c, X_i) v[j][i][s] + sum_{f < F} phi_jf(x_c) w[j][f][s],  s < S <= 64.
 // A wave owns 16 points and all S columns.  v_mfma_f64_16x16x4_f64 with the fragment layout of gemm_f64.hip: lane (l15, lq) supplies
 // A[point l15][row lq] -- it FORMS that element, the covariance of its point (scaled coordinates in registers) with training row i0 + lq
-// (coordinates out of LDS; the cross kernel's arithmetic: kern_decay / kern_value_amp / bocf_exp_nonpos), so the 64 lanes do 64 different
+// (coordinates out of LDS; the cross kernel's arithmetic: kern_of_r2_family), so the 64 lanes do 64 different
 // exponentials per instruction and nothing is computed twice -- and B[row lq][column l15 + 16 t] out of the LDS copy of four rows of v.  One
 // generated operand feeds nt = ceil(S / 16) <= 4 instructions.  The feature sum is the same loop with cos in place of the covariance value,
 // omega in place of X and w in place of v, continuing the same accumulators.
@@ -77,8 +77,7 @@ __global__ __launch_bounds__(256) void path_values_kernel(PathValArgs g) {
           const double dq = xl[r][q] - xc[q];
           r2 += dq * dq;
         }
-        const double u = kern_decay<FAM>(r2);
-        const double a = kern_value_amp<FAM>(variance, r2, u) * bocf_exp_nonpos(-u);
+        const double a = kern_of_r2_family<FAM>(variance, r2);
 #pragma unroll
         for (int t = 0; t < 4; ++t)
           if (t < nt) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, vl[r][16 * t + l15], acc[t], 0, 0, 0);
