@@ -21,6 +21,9 @@ ACQ_EI, ACQ_PI = 0, 1
 UTIL_LINEAR, UTIL_NEG_SQ_DIST, UTIL_NEG_SUM_EXP, UTIL_NEG_EXP_COS, UTIL_ROSENBROCK = 0, 1, 2, 3, 4
 UTIL_PROGRAM = 5        # the utility program staged on the context (bocf_set_utility_program)
 EU_MEAN, EU_CLOSED, EU_MC = 0, 1, 2
+REFINE_LINEAR, REFINE_MC = 0, 1
+# why a row of bocf_refine_acq stopped (RefineReason of csrc/refine_step.h)
+REFINE_REASONS = ("running", "pgtol", "factr", "arc_failed", "maxiter", "maxfun", "nonfinite_start", "nan_gradient")
 EU_MODES = {"mean": EU_MEAN, "closed": EU_CLOSED, "mc": EU_MC}
 
 
@@ -120,6 +123,10 @@ SIGNATURES = {
     "bocf_lbfgsb_batched": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_double_p, ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_double_p, _c_double_p,
                                            _c_ll_p, ctypes.POINTER(ctypes.c_int)]),
+    "bocf_refine_acq": (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p,
+                                       ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                       ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p,
+                                       ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _c_ll_p]),
     "bocf_get_stat": (ctypes.c_int, [_ctx_p, ctypes.c_char_p, _c_ll_p]),
     "bocf_option_count": (ctypes.c_int, []),
     "bocf_option_info": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), _c_ll_p, _c_ll_p, ctypes.POINTER(ctypes.c_int),
@@ -159,6 +166,11 @@ PROBE_SIGNATURES = {
     "bocf_probe_var_i8": (ctypes.c_int, [ctypes.POINTER(ProbeVarI8)]),
     "bocf_probe_tile128": (ctypes.c_int, [ctypes.POINTER(ProbeTile128)]),
 }
+# ... and the hooks of that library that are no launcher probes: refine_advance_kernel on the polynomial of csrc/refine_poly.h
+HOOK_SIGNATURES = {
+    "bocf_refine_probe_poly": (ctypes.c_int, [_c_double_p, _I, _I, _c_double_p, _c_double_p, _I, _I, _D, _D, _I, _D, _I, _I, _c_double_p, _c_double_p,
+                                              _c_int_p, _c_int_p, _c_int_p]),
+}
 
 _libs = {}
 _current = "probes" if os.environ.get("BOCF_PROBES") == "1" else "product"
@@ -176,7 +188,7 @@ def _load(which):
         raise ImportError("%s not found at %s -- build it with `python -m bocf_amd.build%s` "
                           "(there is no CPU fallback)" % (os.path.basename(path), path, "" if which == "product" else " --probes"))
     lib = ctypes.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + (list(PROBE_SIGNATURES.items()) if which == "probes" else []):
+    for name, (res, args) in list(SIGNATURES.items()) + (list(PROBE_SIGNATURES.items()) + list(HOOK_SIGNATURES.items()) if which == "probes" else []):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -359,9 +359,17 @@ class ObjectiveAnchorPointsGenerator(AnchorPointsGenerator):
 
 class AcquisitionOptimizer(object):
     """acquisition_optimizer.py:21-154.  `optimize(f, df, f_df, duplicate_manager, x_baseline)` -> (x_min (1, d),
-    fx_min (1, 1)).  `n_starting` may be raised to tens of thousands: the scoring pass is one device call."""
+    fx_min (1, 1)).  `n_starting` may be raised to tens of thousands: the scoring pass is one device call.
 
-    def __init__(self, space, optimizer='lbfgs', inner_optimizer='lbfgs2', n_starting=400, n_anchor=16, **kwargs):
+    refine="host" (the default) refines the anchors with lbfgsb_batched: one f_df callback per trial step.  refine="device" keeps the
+    loop on the device (multi_outputGP.refine_acq): the same algorithm and settings, no callback; f_df must then be
+    the acquisition_function_withGradients of a covered bocf_amd acquisition (maEI, maPI, EI, PI, uEI_noiseless with a device utility and a
+    full-support parameter distribution) -- anything else raises NotImplementedError, an explicit request never falls back."""
+
+    def __init__(self, space, optimizer='lbfgs', inner_optimizer='lbfgs2', n_starting=400, n_anchor=16, refine="host", **kwargs):
+        if refine not in ("host", "device"):
+            raise ValueError("refine is 'host' or 'device', not %r" % (refine,))
+        self.refine = refine
         self.space = space
         self.optimizer_name = optimizer
         self.inner_optimizer_name = inner_optimizer
@@ -385,6 +393,7 @@ class AcquisitionOptimizer(object):
             raise NotImplementedError("the device path needs f_df (analytical gradients); every bocf_amd acquisition "
                                       "with analytical_gradient_prediction = True passes it (base.py:64-65)")
         self.optimizer = choose_optimizer(self.optimizer_name, self.context_manager.noncontext_bounds)
+        device_objective = self._device_objective(f_df) if self.refine == "device" else None    # (refused before anything runs)
         generator = ObjectiveAnchorPointsGenerator(self.space, random_design_type, f, self.n_starting)
         anchor_points, anchor_points_values = generator.get(num_anchor=self.n_anchor, duplicate_manager=duplicate_manager,
                                                             context_manager=self.context_manager, get_scores=True)
@@ -395,7 +404,10 @@ class AcquisitionOptimizer(object):
             anchor_points = np.vstack((anchor_points, x_baseline))
             anchor_points_values = np.concatenate((anchor_points_values, f_baseline))
         info = {}
-        Xopt, _ = self.optimizer.optimize_batch(anchor_points, f_df, info=info)
+        if self.refine == "device":
+            Xopt = self._refine_on_device(anchor_points, device_objective, info)
+        else:
+            Xopt, _ = self.optimizer.optimize_batch(anchor_points, f_df, info=info)
         fx = np.asarray(f(Xopt), dtype=float).reshape(-1)          # optimizer.py:464: f at every optimum, one batch
         best = int(np.argmin(fx))                                   # min(..., key=fx): first of equal minima
         x_min, fx_min = np.atleast_2d(Xopt[best]), np.atleast_2d(fx[best])
@@ -408,3 +420,20 @@ class AcquisitionOptimizer(object):
         info.update(anchor_points=anchor_points, anchor_points_values=anchor_points_values, optimized_points=Xopt, optimized_values=fx)
         self.last_info = info
         return x_min, fx_min
+
+    def _device_objective(self, f_df):
+        """The device description of the objective, from the acquisition that owns f_df (found through __self__, as
+        ObjectiveAnchorPointsGenerator.select finds the owner of f)."""
+        owner = getattr(f_df, "__self__", None)
+        if owner is None or not hasattr(owner, "device_refine_objective") or getattr(f_df, "__name__", "") != "acquisition_function_withGradients":
+            raise NotImplementedError("refine='device' needs f_df to be the acquisition_function_withGradients of a bocf_amd acquisition "
+                                      "(maEI, maPI, EI, PI, uEI_noiseless): the device loop cannot call a Python f_df; use refine='host'")
+        return owner, owner.device_refine_objective()
+
+    def _refine_on_device(self, anchor_points, device_objective, info):
+        owner, objective = device_objective
+        opt = self.optimizer
+        Xopt, _, dev = owner.model.refine_acq(anchor_points, opt.bounds, maxiter=opt.maxiter, factr=opt.factr, pgtol=opt.pgtol, **objective)
+        info.update(f_df_calls=dev["f_df_calls"], points_evaluated=dev["points_evaluated"], iterations=dev["iterations"],
+                    host_syncs=dev["host_syncs"], reasons=dev["reasons"])
+        return Xopt

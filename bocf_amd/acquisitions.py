@@ -69,6 +69,23 @@ class AcquisitionBase(object):
             raise TypeError("bocf_amd acquisitions need a bocf_amd.multi_outputGP model (no CPU fallback)")
         return self.model
 
+    # -- the device-resident refinement (AcquisitionOptimizer(..., refine="device"))
+    _device_refine = False        # True on the classes the device loop covers
+
+    def device_refine_objective(self):
+        """The objective of acquisition_function_withGradients as keyword arguments of multi_outputGP.refine_acq, or
+        NotImplementedError with the reason: an explicit refine="device" never falls back."""
+        if not type(self)._device_refine:
+            raise NotImplementedError("refine='device' does not cover %s (covered: maEI, maPI, EI, PI, uEI_noiseless); use refine='host'"
+                                      % type(self).__name__)
+        if not self.use_full_support:
+            raise NotImplementedError("refine='device' needs a utility-parameter distribution with full support: without it the host path "
+                                      "draws fresh theta from np.random on every gradient call, which a device loop cannot reproduce; "
+                                      "use refine='host'")
+        if not hasattr(self.model, "refine_acq"):
+            raise TypeError("bocf_amd acquisitions need a bocf_amd.multi_outputGP model (no CPU fallback)")
+        return self._device_refine_kwargs()
+
     def _init_composite(self, cost_withGradients):
         """Constructor tail of the composite-utility acquisitions (uEI_noiseless.py:25-38): W_samples, then -- without full
         support -- ten utility parameters, in this order from np.random."""
@@ -99,6 +116,7 @@ class _ClosedForm(AcquisitionBase):
     analytical_gradient_prediction = True
     _kind = _ffi.ACQ_EI
     _n_theta_samples = 3          # maEI.py:46; maPI.py:46 draws 10
+    _device_refine = True
 
     def __init__(self, model, space, optimizer=None, cost_withGradients=None, utility=None):
         self.optimizer = optimizer
@@ -132,6 +150,12 @@ class _ClosedForm(AcquisitionBase):
         """maEI.py:57-78 / maPI.py:56-76: value and d/dX; not-full-support draws 3 thetas (both classes)."""
         X, (acqX, dacq_dX) = self._evaluate(X, 3, "acq_linear_grad")
         return np.reshape(acqX, (X.shape[0], 1)), np.reshape(dacq_dX, X.shape)
+
+    def _device_refine_kwargs(self):
+        support = self.utility.parameter_dist.support
+        thetas = np.asarray(support, dtype=float).reshape(len(support), -1)
+        return dict(form=_ffi.REFINE_LINEAR, kind=self._kind, thetas=thetas, prob=np.atleast_1d(self.utility.parameter_dist.prob_dist),
+                    n_hyps=self.n_hyps_samples)
 
 
 class maEI(_ClosedForm):
@@ -316,6 +340,17 @@ class _MonteCarlo(AcquisitionBase):
 class uEI_noiseless(_MonteCarlo):
     analytical_gradient_prediction = True
     _kind = _ffi.ACQ_EI
+    _device_refine = True
+
+    def _device_refine_kwargs(self):
+        try:
+            kind = self.utility.device_kind(self.model.output_dim)
+        except NotImplementedError:
+            raise NotImplementedError("refine='device' needs a device utility (Utility(..., device=...), device='program' included): this "
+                                      "utility is a host callable, whose Monte-Carlo loop runs on the host; use refine='host'")
+        return dict(form=_ffi.REFINE_MC, util_kind=kind, util_params=self.utility.device_params,
+                    thetas=device_thetas(kind, self.utility.parameter_dist.support), prob=self.utility_prob_dist, W=self.W_samples,
+                    n_hyps=self.n_hyps_samples, program=self.utility.program_blob if kind == _ffi.UTIL_PROGRAM else None)
 
 
 class uEI_pending(uEI_noiseless):
@@ -332,6 +367,7 @@ class uEI_pending(uEI_noiseless):
     drawn at construction), _compute_acq_withGradients the support or ONE freshly drawn parameter per call.  The pending points are staged
     again whenever the model's fit serial changes.  A utility without a compiled-in device kind raises NotImplementedError."""
     _model_entry = "acq_pending"
+    _device_refine = False        # (its objective has an entry point of its own: outside the device-resident refinement)
 
     def __init__(self, *a, **kw):
         super(uEI_pending, self).__init__(*a, **kw)
@@ -410,6 +446,7 @@ class uEI_constrained(uEI_noiseless):
     Parameter conventions and np.random touchpoints are the parent's.  There is no host fallback: a utility without a compiled-in device
     kind raises NotImplementedError."""
     _model_entry = "acq_mc_constrained"
+    _device_refine = False        # (its objective has an entry point of its own: outside the device-resident refinement)
 
     def __init__(self, model, space, optimizer=None, cost_withGradients=None, utility=None, constraints=None):
         super(uEI_constrained, self).__init__(model, space, optimizer, cost_withGradients=cost_withGradients, utility=utility)

@@ -215,6 +215,10 @@ struct bocf_ctx {
   // state, the incumbent buffers above and bocf_expected_utility's buffers are left as they were
   DevBuf cu_par, cu_val, cu_pof, cu_grad, cu_rng;
   std::vector<double> cu_tail;   // u0 (L) | row_param (C ints) as the tail of util_up's block (kept: its capacity is reused)
+  // ---- device-resident anchor refinement (capi_refine.hip): the rows' state blocks of refine_step.h (doubles; ints with the running-rows
+  // word, the small flag and the column map behind them); for batches above the small path the gathered running rows (rf_x2) and the
+  // whole batch's acquisition and gradient kept across the second predict (rf_acq).  Nothing in them outlives a call.
+  DevBuf rf_dbl, rf_int, rf_x2, rf_acq;
   UtilPack util_up;          // host source of the utility block's upload (util_args.h says why it lives here); kg_par, pd_par, cq_par are its device copies
 };
 
@@ -254,6 +258,15 @@ int bocf_acq_posterior(bocf_ctx* c, bool grad);
 // ... and the one bocf_expected_utility reads (predict_noiseless: no likelihood noise, clipped at 1e-10)
 int bocf_eu_posterior(bocf_ctx* c, bool grad);
 int bocf_copy_pair_out(bocf_ctx* c, const void* src0, double* out0, size_t b0, const void* src1, double* out1, size_t b1);
+// capi.hip, shared with capi_refine.hip: the argument checks of bocf_acq_linear_grad / bocf_acq_mc_grad (outputs per hyper-sample, or -1;
+// errors name `who`), their parameter upload (skipped when nothing changed; *uploaded is set when it ran: one synchronisation), the part of
+// them that only enqueues -- the posterior with its gradients and one acquisition launch per hyper-sample, into c->acq / c->dacq -- and one
+// device word to the host with ONE synchronisation
+int bocf_acq_group_size(bocf_ctx* c, const char* who);
+int bocf_acq_mc_group_size(bocf_ctx* c, const char* who, int util_kind, const double* util_params, int n_util_params, int theta_dim);
+int bocf_acq_upload_params(bocf_ctx* c, const double* theta, int theta_dim, const double* prob, int L, const double* params, int nparams, bool* uploaded);
+int bocf_acq_grad_enqueue(bocf_ctx* c, int m, bool linear, int kind, int util_kind, int n_util_params, int theta_dim, int L);
+int bocf_copy_word_out(bocf_ctx* c, const int* dev, int* out);
 
 
 // HIP-event bracket of a named phase on the context's stream (only with option "profile" = 1; otherwise free)

@@ -363,6 +363,20 @@ void launch_thompson_util_prog(const double* F, int C, int S, const double* thet
 // two-stage top-k (value desc, index asc); out: idx (k) int64, val (k)
 void launch_topk(const double* acq, int C, int k, long long* blk_idx, double* blk_val, long long* out_idx, double* out_val, hipStream_t s);
 int topk_num_blocks(int C);
+// device-resident anchor refinement (refine.hip; the step itself is refine_step.h).  init: fresh rows from the clamped resident candidates
+// Xc (A, d) into zeroed state blocks, running = A.  advance: every running row consumes -acq / -dacq at its trial point and writes its next
+// one (a stopped row its final x) into Xc; running is decremented once per row that stops.  d <= REFINE_MAX_D, one workgroup per row.
+struct RefineSettings;
+void launch_refine_init(double* Xc, double* dbl, int* ints, int* running, int A, const RefineSettings& s, hipStream_t st);
+void launch_refine_advance(const double* acq, const double* dacq, double* Xc, double* dbl, int* ints, int* running, int A, const RefineSettings& s,
+                           const double* lo, const double* hi, hipStream_t st, const double* acq2 = nullptr, const double* dacq2 = nullptr,
+                           const int* map = nullptr, const int* small = nullptr);
+// A > BOCF_SMALL_N: the first BOCF_SMALL_N running rows of Xc gathered in row order into x2 (BOCF_SMALL_N, d), map[row] = its column there
+// (-1: stopped), *small = no more than BOCF_SMALL_N rows run; launch_refine_advance then reads acq2 / dacq2 (of x2) when *small
+void launch_refine_compact(const double* Xc, const int* ints, int A, int d, double* x2, int* map, int* small, hipStream_t st);
+#ifdef BOCF_PROBES
+void launch_refine_poly(const double* Xc, int A, int d, double* acq, double* dacq, hipStream_t st);   // -f, -g of refine_poly.h at the rows
+#endif
 // multi-GPU selection: pack the k local winners (+ lo) into a 2 * world * k buffer of doubles; merge the gathered buffer
 void launch_pack_topk(const long long* idx, const double* val, int k, long long lo, int world, int rank, double* pack, hipStream_t s);
 void launch_merge_packed(const double* pack, int k, int world, long long* gidx, double* gval, long long* out_idx, double* out_val, hipStream_t s);

@@ -114,7 +114,7 @@ extern "C" void bocf_destroy(bocf_ctx* c) {
                     &c->kg_par, &c->kg_v0, &c->kg_astar, &c->kg_AB, &c->kg_out, &c->kg_dout, &c->prog_buf,
                     &c->pd_XP, &c->pd_VP, &c->pd_Wp, &c->pd_muP, &c->pd_cov, &c->pd_pack, &c->pd_QFG, &c->pd_par, &c->pd_best, &c->pd_T, &c->pd_muc, &c->pd_E,
                     &c->pt_E, &c->pt_g, &c->pt_rhs, &c->pt_tmp, &c->pt_nug, &c->pt_par, &c->pt_rows, &c->pt_tab, &c->pt_pv, &c->pt_pg, &c->pt_val, &c->pt_grad,
-                    &c->cq_tab, &c->cq_par, &c->cq_best, &c->cq_nf, &c->cu_par, &c->cu_val, &c->cu_pof, &c->cu_grad, &c->cu_rng};
+                    &c->cq_tab, &c->cq_par, &c->cq_best, &c->cq_nf, &c->cu_par, &c->cu_val, &c->cu_pof, &c->cu_grad, &c->cu_rng, &c->rf_dbl, &c->rf_int, &c->rf_x2, &c->rf_acq};
   for (DevBuf* b : bufs) b->release();
   if (c->infer_out) (void)hipHostFree(c->infer_out);
   if (c->tile_ctr) (void)hipFree(c->tile_ctr);
@@ -580,7 +580,9 @@ extern "C" int bocf_mean_at_train(bocf_ctx* c, double* out) {
   return 0;
 }
 
-static int upload_acq_params(bocf_ctx* c, const double* theta, int theta_dim, const double* prob, int L, const double* params, int nparams) {
+// (uploaded, when given: set when the parameters went up, which costs one stream synchronisation)
+static int upload_acq_params(bocf_ctx* c, const double* theta, int theta_dim, const double* prob, int L, const double* params, int nparams,
+                             bool* uploaded = nullptr) {
   if (L < 1 || L > BOCF_MAX_L) return fail("acquisition", "L out of range (1..32)");
   std::vector<double> th((size_t)L * (theta_dim > 0 ? theta_dim : 1), 0.0), pr(L), pa(BOCF_MAX_M, 0.0);
   if (theta_dim > 0) {
@@ -608,6 +610,7 @@ static int upload_acq_params(bocf_ctx* c, const double* theta, int theta_dim, co
   HIPCHK(hipStreamSynchronize(c->stream));
   c->last_params.swap(key);
   c->best_epoch = -1;                                    // the best-so-far values belong to the old parameters
+  if (uploaded) *uploaded = true;
   return 0;
 }
 
@@ -675,14 +678,10 @@ static void acq_over_hyper_samples(bocf_ctx* c, AcqArgs a, int m, int linear, Ac
   }
 }
 
-// What the four acquisitions share once their arguments are checked: the parameters go up (only when they changed), the posterior -- with
-// its input gradients for the _grad forms -- of every resident candidate, one launch per hyper-sample, values (and gradients) to the host.
-// linear: the linear-utility forms (EI / PI of theta^T f); theta_dim as the caller gave it; the Monte-Carlo forms read the resident samples.
-static int run_acq(bocf_ctx* c, int m, bool linear, bool grad, AcqLaunch launch, int kind, int util_kind, const double* util_params, int n_util_params,
-                   const double* theta, int theta_dim, const double* prob, int L, double* acq_out, double* dacq_out) {
-  HIPCHK(hipSetDevice(c->device));
-  if (c->C == 0) return 0;
-  if (upload_acq_params(c, theta, theta_dim, prob, L, util_params, n_util_params)) return -1;
+// The part of an acquisition that only enqueues, with the parameters already on the device: the posterior -- with its input gradients
+// for the _grad forms -- of every resident candidate and one launch per hyper-sample; c->acq (and c->dacq) hold the result once the stream
+// gets there.  Shared by run_acq and, once per pass, by the device-resident refinement (capi_refine.hip).
+static int acq_enqueue(bocf_ctx* c, int m, bool linear, bool grad, AcqLaunch launch, int kind, int util_kind, int n_util_params, int theta_dim, int L) {
   // model.predict (maEI.py:87) / posterior_mean + posterior_variance (uEI_noiseless.py:73-74)
   if (run_predict(c, BOCF_ADD_NOISE | BOCF_CLIP, true, grad)) return -1;
   AcqArgs a{};
@@ -695,6 +694,18 @@ static int run_acq(bocf_ctx* c, int m, bool linear, bool grad, AcqLaunch launch,
   if (grad) { a.dmean = c->dmean.as<double>(); a.dvar = c->dvar.as<double>(); a.ldg = c->pred_cap; a.d = c->d; a.dacq = c->dacq.as<double>(); }
   acq_over_hyper_samples(c, a, m, linear ? 1 : 0, launch);
   c->have_acq = true;
+  return 0;
+}
+
+// What the four acquisitions share once their arguments are checked: the parameters go up (only when they changed), the enqueue part above,
+// values (and gradients) to the host.
+// linear: the linear-utility forms (EI / PI of theta^T f); theta_dim as the caller gave it; the Monte-Carlo forms read the resident samples.
+static int run_acq(bocf_ctx* c, int m, bool linear, bool grad, AcqLaunch launch, int kind, int util_kind, const double* util_params, int n_util_params,
+                   const double* theta, int theta_dim, const double* prob, int L, double* acq_out, double* dacq_out) {
+  HIPCHK(hipSetDevice(c->device));
+  if (c->C == 0) return 0;
+  if (upload_acq_params(c, theta, theta_dim, prob, L, util_params, n_util_params)) return -1;
+  if (acq_enqueue(c, m, linear, grad, launch, kind, util_kind, n_util_params, theta_dim, L)) return -1;
   const size_t b0 = acq_out ? sizeof(double) * (size_t)c->C : 0, b1 = dacq_out ? sizeof(double) * (size_t)c->C * c->d : 0;
   return copy_pair_out(c, c->acq.p, acq_out, b0, c->dacq.p, dacq_out, b1);
 }
@@ -761,6 +772,31 @@ extern "C" int bocf_acq_mc_grad(bocf_ctx* c, int util_kind, const double* util_p
   if (m < 0) return -1;
   if (c->d > 64) return fail("bocf_acq_mc_grad", "input dimension too large");
   return run_acq(c, m, false, true, launch_acq_mc_grad, BOCF_ACQ_EI, util_kind, util_params, n_util_params, theta, theta_dim, prob, L, acq_out, dacq_out);
+}
+
+// ---- for capi_refine.hip (declared in bocf_ctx.h): the checks, the parameter upload and the enqueue part of the gradient acquisitions
+int bocf_acq_group_size(bocf_ctx* c, const char* who) { return group_size(c, who); }
+int bocf_acq_mc_group_size(bocf_ctx* c, const char* who, int util_kind, const double* util_params, int n_util_params, int theta_dim) {
+  return mc_group_size(c, who, util_kind, util_params, n_util_params, theta_dim);
+}
+int bocf_acq_upload_params(bocf_ctx* c, const double* theta, int theta_dim, const double* prob, int L, const double* params, int nparams, bool* uploaded) {
+  return upload_acq_params(c, theta, theta_dim, prob, L, params, nparams, uploaded);
+}
+int bocf_acq_grad_enqueue(bocf_ctx* c, int m, bool linear, int kind, int util_kind, int n_util_params, int theta_dim, int L) {
+  return acq_enqueue(c, m, linear, true, linear ? launch_acq_linear_grad : launch_acq_mc_grad, linear ? kind : BOCF_ACQ_EI, util_kind, n_util_params,
+                     theta_dim, L);
+}
+// one device word to the host through the pinned buffer: ONE stream synchronisation
+int bocf_copy_word_out(bocf_ctx* c, const int* dev, int* out) {
+  if (pin_ensure(&c->pin_out, &c->pin_out_cap, sizeof(int)) == 0) {
+    HIPCHK(hipMemcpyAsync(c->pin_out, dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *out = *static_cast<const int*>(c->pin_out);
+    return 0;
+  }
+  HIPCHK(hipMemcpyAsync(out, dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 extern "C" int bocf_set_eu_samples(bocf_ctx* c, const double* Z, int L, int S) {

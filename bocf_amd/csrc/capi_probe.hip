@@ -9,7 +9,9 @@
 // tests/gemm_ref.py states the same contract in NumPy; tests/test_gpu_gemm_kernels.py compares the two.
 #ifdef BOCF_PROBES
 #include "bocf_ctx.h"
+#include "refine_step.h"
 
+#include <cmath>
 #include <cstdio>
 
 namespace {
@@ -265,6 +267,52 @@ int bocf_probe_tile128(bocf_probe_tile128_desc* d) {
   }
   if (sc.down(d->A, dA, nA) || sc.down(d->B, dB, nB) || sc.down(d->C, dC, nC)) return -1;
   return sc.finish();
+}
+
+// (Not one of the launcher probes above, hence not named like them.)  The refinement's state machine on the device alone: refine_advance_kernel on the polynomial of refine_poly.h in the place of the
+// acquisition pass, `passes` times, from the clamped rows of X0 (A, d).  Outputs as bocf_refine_acq's (F_out = the polynomial).
+int bocf_refine_probe_poly(const double* X0, int A, int d, const double* lo, const double* hi, int maxiter, int m, double factr, double pgtol, int max_ls,
+                           double c1, int maxfun, int passes, double* X_out, double* F_out, int* iters_out, int* nfun_out, int* reason_out) {
+  const char* who = "bocf_refine_probe_poly";
+  if (!X0 || !lo || !hi || !X_out || !F_out || !iters_out || !nfun_out || !reason_out) return probe_fail(who, "null argument");
+  if (A < 1 || A > 64 || d < 1 || d > REFINE_MAX_D || m < 1 || m > REFINE_MAX_M || max_ls < 1 || maxiter < 0 || passes < 0)
+    return probe_fail(who, "need 1 <= A <= 64, 1 <= d <= 64, 1 <= m <= 64, max_ls >= 1, maxiter >= 0, passes >= 0");
+  for (int k = 0; k < d; ++k)
+    if (!(lo[k] <= hi[k])) return probe_fail(who, "lo > hi");
+  RefineSettings s;
+  s.d = d; s.m = m; s.maxiter = maxiter; s.max_ls = max_ls; s.maxfun = maxfun < 0 ? -1 : maxfun;
+  s.factr = factr; s.pgtol = pgtol; s.c1 = c1; s.boxed = refine_boxed(lo, hi, d);
+  std::vector<double> Xcl((size_t)A * d);
+  for (int a = 0; a < A; ++a)
+    for (int k = 0; k < d; ++k) Xcl[(size_t)a * d + k] = std::fmin(std::fmax(X0[(size_t)a * d + k], lo[k]), hi[k]);
+  ProbeScope sc;
+  if (sc.open()) return -1;
+  const size_t nd = (size_t)A * refine_row_doubles(d, m), ni = (size_t)A * REFINE_ROW_INTS + 1;
+  double *Xc = nullptr, *acq = nullptr, *dacq = nullptr, *dbl = nullptr;
+  int* ints = nullptr;
+  if (sc.alloc(&Xc, (size_t)A * d) || sc.alloc(&acq, (size_t)A) || sc.alloc(&dacq, (size_t)A * d) || sc.alloc(&dbl, nd) || sc.alloc(&ints, ni)) return -1;
+  if (sc.up(Xc, Xcl.data(), (size_t)A * d)) return -1;
+  HIPCHK(hipMemsetAsync(dbl, 0, sizeof(double) * nd, sc.s));
+  HIPCHK(hipMemsetAsync(ints, 0, sizeof(int) * ni, sc.s));
+  int* running = ints + (size_t)A * REFINE_ROW_INTS;
+  launch_refine_init(Xc, dbl, ints, running, A, s, sc.s);
+  for (int p = 0; p < passes; ++p) {
+    launch_refine_poly(Xc, A, d, acq, dacq, sc.s);
+    launch_refine_advance(acq, dacq, Xc, dbl, ints, running, A, s, lo, hi, sc.s);
+  }
+  std::vector<double> hd(nd);
+  std::vector<int> hints(ni);
+  if (sc.down(hd.data(), dbl, nd) || sc.down(hints.data(), ints, ni)) return -1;
+  if (sc.finish()) return -1;
+  for (int a = 0; a < A; ++a) {
+    const RefineRow r = refine_row_view(hd.data() + (size_t)a * refine_row_doubles(d, m), hints.data() + (size_t)a * REFINE_ROW_INTS, d, m);
+    for (int k = 0; k < d; ++k) X_out[(size_t)a * d + k] = r.x[k];
+    F_out[a] = *r.f;
+    iters_out[a] = *r.iters;
+    nfun_out[a] = *r.nfun;
+    reason_out[a] = *r.reason;
+  }
+  return 0;
 }
 
 }  // extern "C"

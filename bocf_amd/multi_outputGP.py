@@ -1088,6 +1088,45 @@ class multi_outputGP(object):
             _ffi.check(getattr(_ffi.load(), name)(self._context().handle, *head, *util, *extra, _ffi.dptr(acq), _ffi.dptr(dacq)), name)
         return (acq, dacq) if grad else acq
 
+    REFINE_POLL_EVERY = 8      # passes between two reads of the running-rows word (the sweep is in DESIGN.md section 19)
+
+    def refine_acq(self, X0, bounds, form, kind=_ffi.ACQ_EI, util_kind=_ffi.UTIL_LINEAR, util_params=None, thetas=None, prob=None, W=None,
+                   n_hyps=None, program=None, maxiter=500, m=10, factr=1e6, pgtol=1e-5, max_ls=20, c1=1e-4, maxfun=None, poll_every=None):
+        """Refine the rows of X0 (A <= 64, d) inside the box `bounds` with the loop on the device (bocf_refine_acq): minimises -acq of
+        form _ffi.REFINE_LINEAR (closed-form EI / PI `kind` of theta . f, as acq_linear_grad) or _ffi.REFINE_MC (Monte-Carlo EI of the
+        utility block, as acq_mc_grad; W and a program go up as there) with the algorithm and settings of lbfgsb_batched.  Returns
+        (X (A, d), F (A,) = -acq there, info): iterations, evaluations and reasons (names of _ffi.REFINE_REASONS) per row, passes,
+        points_evaluated, host_syncs.  Afterwards no candidates and no acquisition vector are resident."""
+        self._begin_acq(n_hyps, form == _ffi.REFINE_LINEAR)
+        if form == _ffi.REFINE_MC:
+            if util_kind == _ffi.UTIL_PROGRAM:
+                self.set_utility_program(program)
+            if W is not None:
+                self.set_mc_samples(W)
+        X0 = _ffi.f64(np.atleast_2d(X0))
+        A, d = X0.shape
+        if d != self._X.shape[1]:
+            raise ValueError("starts must be (A, %d)" % self._X.shape[1])
+        lo = _ffi.f64([b[0] for b in bounds])
+        hi = _ffi.f64([b[1] for b in bounds])
+        if lo.shape != (d,):
+            raise ValueError("bounds must be %d (lo, hi) pairs" % d)
+        if form == _ffi.REFINE_LINEAR and (thetas is None or np.atleast_2d(thetas).shape[1] != self.output_dim):
+            raise ValueError("theta must have output_dim entries")     # (the library reads L rows of output_dim doubles)
+        util = self._utility_args(util_params, thetas, prob)
+        X, F = np.empty((A, d)), np.empty(A)
+        iters, nfun, reason = (np.zeros(A, dtype=np.int32) for _ in range(3))
+        counters = (ctypes.c_longlong * 2)()
+        ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        self._resident.forget("candidates")                # the batch and its acquisition vector are the loop's from here on
+        _ffi.check(_ffi.load().bocf_refine_acq(self._context().handle, int(form), int(kind), int(util_kind), *util, _ffi.dptr(X0), A, _ffi.dptr(lo),
+                                               _ffi.dptr(hi), int(maxiter), int(m), float(factr), float(pgtol), int(max_ls), float(c1),
+                                               -1 if maxfun is None else int(maxfun), int(self.REFINE_POLL_EVERY if poll_every is None else poll_every),
+                                               _ffi.dptr(X), _ffi.dptr(F), ip(iters), ip(nfun), ip(reason), counters), "bocf_refine_acq")
+        info = dict(iterations=iters.astype(int), evaluations=nfun.astype(int), reasons=[_ffi.REFINE_REASONS[r] for r in reason],
+                    passes=int(counters[0]), f_df_calls=int(counters[0]), points_evaluated=int(nfun.sum()), host_syncs=int(counters[1]))
+        return X, F, info
+
     def _device_utility(self, utility):
         """(kind, params) of a Utility for the device; a utility program is staged."""
         kind = utility.device_kind(self.output_dim)

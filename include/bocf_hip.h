@@ -627,6 +627,30 @@ int bocf_lbfgsb_batched(bocf_fdf_callback f_df, void* user, const double* X0, in
                         int m, double factr, double pgtol, int max_ls, double c1, int maxfun, double* X_out, double* F_out,
                         long long* calls_out, int* iters_out);
 
+/* ---- the same refinement with the loop on the device.  The rows of X0 (A, d), 1 <= A <= 64, are clamped into the
+ * box lo, hi (d; infinite allowed, lo <= hi) and become the resident candidate batch; every pass enqueues the posterior with its input
+ * gradients and the acquisition of the resident rows -- what bocf_acq_linear_grad (form BOCF_REFINE_LINEAR, `kind` = BOCF_ACQ_EI / _PI;
+ * theta (L, m), the utility arguments before it are ignored) or bocf_acq_mc_grad (form BOCF_REFINE_MC; `kind` ignored; the utility block as
+ * there, a resident utility program included) enqueue -- and one launch that advances every running row by one evaluation of the state
+ * machine of csrc/refine_step.h (minimising -acq: the algorithm, settings and stopping tests of bocf_lbfgsb_batched, maxfun < 0 = none)
+ * and writes its next trial point into the resident rows.  No callback, no per-pass copy: after every poll_every >= 1 passes the host
+ * reads one word (rows still running) and stops enqueueing at zero or when the pass budget min(1 + maxiter max_ls, maxfun + max_ls) is
+ * spent; rows are frozen once stopped, so the results do not depend on poll_every.  A batch of more than 16 rows is predicted twice per
+ * pass (the whole batch, and its first 16 running rows, read once no more run; the whole batch is dropped once a poll shows that no more
+ * run), so that every point goes through the kernels the host loop would use for it: about 0.7 ms instead of 0.13 ms per pass at N = 1024
+ * until then (DESIGN.md section 19 has the figures).  X_out (A, d), F_out (A) = -acq there; iters_out,
+ * nfun_out (evaluations), reason_out (A each, or NULL): per row, reason one of RefineReason of csrc/refine_step.h (1 pgtol, 2 relative
+ * decrease, 3 arc search failed, 4 maxiter, 5 maxfun, 6 non-finite start, 7 NaN gradient); counters_out[2] (or NULL) = passes enqueued,
+ * host synchronisations.  Afterwards the resident candidates are the final points and the context serves no acquisition vector.  Every
+ * refusal of an argument names bocf_refine_acq and happens before the context is touched (the resident batch is replaced last of the
+ * steps that can fail before the first launch). */
+enum { BOCF_REFINE_LINEAR = 0, BOCF_REFINE_MC = 1 };
+#define BOCF_REFINE_MAX_ROWS 64
+int bocf_refine_acq(bocf_ctx* ctx, int form, int kind, int util_kind, const double* util_params, int n_util_params, const double* theta,
+                    int theta_dim, const double* prob, int L, const double* X0, int A, const double* lo, const double* hi, int maxiter, int m,
+                    double factr, double pgtol, int max_ls, double c1, int maxfun, int poll_every, double* X_out, double* F_out,
+                    int* iters_out, int* nfun_out, int* reason_out, long long* counters_out);
+
 #ifdef __cplusplus
 }
 #endif
