@@ -324,6 +324,11 @@ class CBO(object):
 
     plot_acquisition = plot_convergence = integrated_plot
 
+    def model_check(self):
+        """Leave-one-out check of the surrogate the loop currently rests on (model.loo_summary(): per output the log pseudo-likelihood,
+        the rmse and the calibration of the standardised residuals).  On request only: run_optimization never calls it."""
+        return self.model.loo_summary()
+
     # ---- the loop ------------------------------------------------------------------------------------------------------------
     def run_optimization(self, max_iter=1, parallel=False, plot=False, results_file=None, max_time=np.inf, eps=1e-8, context=None,
                          verbosity=False):

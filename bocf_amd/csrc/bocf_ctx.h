@@ -219,7 +219,12 @@ struct bocf_ctx {
   // word, the small flag and the column map behind them); for batches above the small path the gathered running rows (rf_x2) and the
   // whole batch's acquisition and gradient kept across the second predict (rf_acq).  Nothing in them outlives a call.
   DevBuf rf_dbl, rf_int, rf_x2, rf_acq;
-  UtilPack util_up;          // host source of the utility block's upload (util_args.h says why it lives here); kg_par, pd_par, cq_par are its device copies
+  // ---- leave-one-out cross-validation (capi_loo.hip): mean | variance | log density (m, Np each) and their sums (m), the per-output
+  // diagonal shift, and the parameters, rows and values of bocf_loo_utility in buffers of their own.  Every call recomputes what it reads
+  // from R and alpha, so no fit, append or target update has anything to invalidate here.
+  DevBuf loo_out, loo_sum, loo_shift, loo_par, loo_rows, loo_val;
+  std::vector<double> loo_shift_host;   // source of the shift's upload (kept: the copy is asynchronous)
+  UtilPack util_up;         // host source of the utility block's upload (util_args.h says why it lives here); kg_par, pd_par, cq_par are its device copies
 };
 
 // hyper-samples the acquisitions average over: option acq_hyper_samples, or (0, or more than are resident) all of option hyper_samples (1 .. 64)

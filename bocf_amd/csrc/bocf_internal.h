@@ -212,6 +212,13 @@ void launch_pack_upper_tiles(const double* R, int Np, double* packed, hipStream_
 void launch_unpack_upper_tiles(const double* packed, int Np, double* R, hipStream_t s);
 // alpha = R t (t = R^T y comes from launch_gemv_small_t)
 void launch_gemv_upper_n(const double* R, long strideR, int Np, const double* t, double* alpha, int m, hipStream_t s);
+// loo.hip: leave-one-out mean / variance / log predictive density of every training point from R and alpha ((m, ld) each, first N columns;
+// shift (m) = what the fit added to the diagonal besides the noise; flags = BOCF_ADD_NOISE / BOCF_CLIP as for a prediction), the sums of
+// the densities over the points, and the parameter-index rows (L, N) of the expected-utility launches over those posteriors
+void launch_loo(const double* R, long strideR, int N, int Np, const double* alpha, const double* yc, const KernHyp* hyp, const double* shift, int flags,
+                double* mu, double* var, double* lpd, long ld, int m, hipStream_t s);
+void launch_loo_sum(const double* lpd, long ld, int N, double* out, int m, hipStream_t s);
+void launch_loo_rows(int* rows, int N, int L, hipStream_t s);
 // Rank-1 append of one observation (row/column N of the padded factor; requires N < Np).  u = R^T k_new (Np),
 // w = R u (Np), sumsq = ||u||^2 per output.  On a non-positive pivot fail[j] = 1 and nothing is written.
 void launch_append_write(double* S, double* R, double* RT, long strideS, double* E, double* ET, long strideE, int Np, int N,

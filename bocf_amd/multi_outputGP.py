@@ -1359,6 +1359,124 @@ class multi_outputGP(object):
             self._current_h = min(n_h, self._H) - 1
         return (val, pof, dval) if grad else (val, pof)
 
+    # ---- leave-one-out cross-validation of the resident model ------------------------------------------------
+    def _loo(self, flags, mean=False, var=False, lpd=False, total=False):
+        """One bocf_loo over all H * m factorizations; only the arrays asked for are transferred (None for the others)."""
+        self._ensure_fitted()
+        M, N = self.output_dim * self._H, self._X.shape[0]
+        out = [np.empty((M, N)) if want else None for want in (mean, var, lpd)] + [np.empty(M) if total else None]
+        _ffi.check(_ffi.load().bocf_loo(self._context().handle, flags, *[_ffi.dptr(a) for a in out]), "bocf_loo")
+        return out
+
+    def _loo_rows(self, a, all_hyper_samples):
+        if all_hyper_samples:
+            return a.reshape((self._H, self.output_dim) + a.shape[1:])
+        return a[self._rows()].copy()
+
+    def loo(self, noiseless=False, all_hyper_samples=False):
+        """Leave-one-out predictions at the training points from the resident factor (ExactGaussianInference.LOO,
+        exact_gaussian_inference.py:67-79, and the predictive moments its densities are made of): (mean, var, lpd), each (m, N) -- point i
+        predicted by the model of the other N - 1 points, hyper-parameters and the targets' centre held.  The variance includes the
+        likelihood noise unless `noiseless` and is clipped at 1e-10 (as predict / predict_noiseless); lpd is the log density of y_i under
+        the prediction with noise, whatever `noiseless`.  The current hyper-sample answers; all_hyper_samples=True gives (H, m, N) each."""
+        flags = _ffi.CLIP | (0 if noiseless else _ffi.ADD_NOISE)
+        mean, var, lpd, _ = self._loo(flags, mean=True, var=True, lpd=True)
+        return tuple(self._loo_rows(a, all_hyper_samples) for a in (mean, var, lpd))
+
+    def loo_log_likelihood(self, all_hyper_samples=False):
+        """Leave-one-out log pseudo-likelihood sum_i lpd_i per output: (m,), or (H, m).  Only the sums leave the device."""
+        return self._loo_rows(self._loo(_ffi.ADD_NOISE | _ffi.CLIP, total=True)[3], all_hyper_samples)
+
+    @staticmethod
+    def loo_summary_of(Y, mean, var, lpd):
+        """The summary of leave-one-out results Y, mean, var (with noise), lpd, each (m, N): per output the pseudo-likelihood `lpd`, the
+        `rmse` of the mean, mean `z_mean` and variance `z_var` of the standardised residuals z = (y - mean) / sqrt(var), and the share
+        `coverage` of |z| <= 1.96 (0.95 for a calibrated model)."""
+        Y, mean, var, lpd = (np.asarray(a, dtype=float) for a in (Y, mean, var, lpd))
+        z = (Y - mean) / np.sqrt(var)
+        return {"lpd": lpd.sum(1), "rmse": np.sqrt(np.mean((Y - mean) ** 2, 1)), "z_mean": z.mean(1), "z_var": z.var(1),
+                "coverage": np.mean(np.abs(z) <= 1.96, 1)}
+
+    def loo_summary(self):
+        """loo_summary_of the current hyper-sample's leave-one-out predictions: a dict of (m,) arrays."""
+        mean, var, lpd = self.loo()
+        return self.loo_summary_of(np.stack([y[:, 0] for y in self._Y], 0), mean, var, lpd)
+
+    def loo_utility(self, utility, parameters=None, noiseless=False, Z=None, n_samples=50):
+        """The cross-validated composite prediction: (predicted (L, N), observed (L, N)) with predicted[l, i] = E[U(theta_l, y)] under the
+        leave-one-out prediction of training point i (bocf_loo_utility, current hyper-sample; with the likelihood noise unless
+        `noiseless`) and observed[l, i] = U(theta_l, y_i) from the utility's host callable.  `parameters` (L, theta_dim) defaults to the
+        support of utility.parameter_dist.  The expectation takes the form the recommendation step takes for this utility: the mean for a
+        linear one, the closed form where the device has one, else the mean over the normals Z (L, S, m) (default: n_samples draws per
+        parameter from np.random.normal).  A utility outside the device set raises NotImplementedError: there is no host fallback."""
+        from .utility import device_thetas, inner_expectation
+        m = self.output_dim
+        mode, kind = inner_expectation(utility, m)           # (raises before anything touches the device)
+        self._ensure_fitted()
+        N = self._X.shape[0]
+        if parameters is None:
+            parameters = getattr(utility.parameter_dist, "support", None)
+            if parameters is None:
+                raise ValueError("the utility's parameter distribution has no support: give `parameters`")
+        parameters = np.asarray(parameters, dtype=float).reshape(len(parameters), -1)
+        L = parameters.shape[0]
+        if kind == _ffi.UTIL_PROGRAM:
+            self.set_utility_program(utility.program_blob)
+        if mode == _ffi.EU_MC:
+            self.set_eu_samples(np.random.normal(size=(L, int(n_samples), m)) if Z is None else Z)
+        params, n_params, th, tdim, _, _ = self._utility_args(utility.device_params, device_thetas(kind, parameters), None)
+        predicted = np.empty((L, N))
+        flags = _ffi.CLIP | (0 if noiseless else _ffi.ADD_NOISE)
+        _ffi.check(_ffi.load().bocf_loo_utility(self._context().handle, self._current_h, flags, mode, kind, params, n_params, th, tdim, L,
+                                                _ffi.dptr(predicted)), "bocf_loo_utility")
+        Y = np.stack([y[:, 0] for y in self._Y], 0)
+        observed = np.array([[float(np.squeeze(utility.func(parameters[l], Y[:, i]))) for i in range(N)] for l in range(L)])
+        return predicted, observed
+
+    def loo_compare(self, kernel_lists):
+        """Score F candidate kernel lists (each one kernel per output, hyper-parameters as given) on the current data: the (F, m) tables
+        (leave-one-out log pseudo-likelihood, log marginal likelihood).  The F x m models are fitted as F groups of m outputs in ONE
+        bocf_fit on a context of their own -- the resident model is not touched.  Fixed hyper-parameters only (ValueError otherwise:
+        learned ones would have to be re-learned per family)."""
+        if not self.fixed_hyps:
+            raise ValueError("loo_compare / select_kernels compare kernels at fixed hyper-parameters (fixed_hyps=True)")
+        if self._X is None:
+            raise RuntimeError("updateModel has not been called")
+        kernel_lists = [list(kl) for kl in kernel_lists]
+        F, m = len(kernel_lists), self.output_dim
+        if F < 1 or any(len(kl) != m for kl in kernel_lists):
+            raise ValueError("kernel_lists must hold lists of output_dim kernels")
+        N, d = self._X.shape
+        specs = [kernel_spec(k, d) for kl in kernel_lists for k in kl]
+        kids = [int(s[0]) for s in specs]
+        var, ls = _ffi.f64([s[1] for s in specs]), _ffi.f64([s[2] for s in specs])
+        noise = _ffi.f64(np.tile([1e-10 if nv is None else float(nv) for nv in self.noise_var], F))
+        Y = _ffi.f64(np.tile(np.stack([y[:, 0] for y in self._Y], 0), (F, 1)))
+        lib, ctx = _ffi.load(), _ffi.Context(self.device)
+        try:
+            ctx.set_option("hyper_samples", F)
+            if len(set(kids)) > 1:
+                _ffi.check(lib.bocf_set_kernel_ids(ctx.handle, (ctypes.c_int * len(kids))(*kids), len(kids)), "bocf_set_kernel_ids")
+            jit, lml, loo = np.zeros(F * m), np.zeros(F * m), np.zeros(F * m)
+            rc = _ffi.check(lib.bocf_fit(ctx.handle, _ffi.dptr(self._X), _ffi.dptr(Y), N, d, F * m, kids[0], _ffi.dptr(var), _ffi.dptr(ls),
+                                         _ffi.dptr(noise), 5, _ffi.dptr(jit), _ffi.dptr(lml)), "bocf_fit")
+            if rc > 0:
+                raise np.linalg.LinAlgError("not positive definite, even with jitter.")
+            _ffi.check(lib.bocf_loo(ctx.handle, _ffi.ADD_NOISE | _ffi.CLIP, None, None, None, _ffi.dptr(loo)), "bocf_loo")
+        finally:
+            ctx.close()
+        return loo.reshape(F, m), lml.reshape(F, m)
+
+    def select_kernels(self, kernel_lists, criterion="loo"):
+        """Per output the kernel of the candidate list that scores best in loo_compare's table -- criterion "loo" (log pseudo-likelihood)
+        or "lml" (log marginal likelihood); ties to the earlier list.  Returns a kernel list to build a model from."""
+        if criterion not in ("loo", "lml"):
+            raise ValueError("criterion must be 'loo' or 'lml'")
+        kernel_lists = [list(kl) for kl in kernel_lists]
+        table = self.loo_compare(kernel_lists)[0 if criterion == "loo" else 1]
+        best = np.argmax(np.asarray(table), axis=0)
+        return [kernel_lists[int(best[j])][j] for j in range(self.output_dim)]
+
     def select_topk(self, k):
         """(indices, values) of the k best candidates of the last acquisition call -- the
         np.argsort(-acq)[:k] of anchor_points_generator.py:61, ties to the lowest index.  A NaN

@@ -651,6 +651,33 @@ int bocf_refine_acq(bocf_ctx* ctx, int form, int kind, int util_kind, const doub
                     double factr, double pgtol, int max_ls, double c1, int maxfun, int poll_every, double* X_out, double* F_out,
                     int* iters_out, int* nfun_out, int* reason_out, long long* counters_out);
 
+/* ---- leave-one-out cross-validation of the resident model (ExactGaussianInference.LOO,
+ * GPy/inference/latent_function_inference/exact_gaussian_inference.py:67-79).  For factorization j with the fit's own
+ * Ky = K + (noise_j + 1e-8 + jitter_j) I, yc = y - ymean_j (the centre and the hyper-parameters are held when a point is left out, as
+ * GPy's LOO holds them), alpha = Ky^-1 yc, c_i = (Ky^-1)_ii = sum_{k >= i} R[i][k]^2 from the resident inverse factor, shift = 1e-8 + jitter_j:
+ *   mu_loo[i]  = y_i - alpha_i / c_i
+ *   var_loo[i] = 1 / c_i - shift              with BOCF_ADD_NOISE (the likelihood noise stays in), - noise_j more without;
+ *                                             clipped at 1e-10 under BOCF_CLIP: the flags mean what they mean for a prediction
+ *   lpd[i]     = -0.5 log 2 pi + 0.5 log c_i - 0.5 alpha_i^2 / c_i      (:73-79 to the letter: nothing removed from 1 / c_i)
+ *   lpd_sum[j] = sum_{i < N} lpd[i]           (summed in a fixed order)
+ * for all M = H m resident factorizations, hyper-sample-major: mean_out, var_out, lpd_out (M,N), lpd_sum_out (M), each or all NULL.  One
+ * pass over the upper triangles of R instead of N refits; two calls give the same bits.
+ *
+ * bocf_loo_utility: val_out (L,N), entry (l, i) = E[U(theta_l, y)], y ~ N(mu_loo[:, i], diag var_loo[:, i]) over the outputs of hyper-sample
+ * `group` (0 .. H - 1) -- the cross-validated prediction of the composite objective at training point i.  `mode` as for the expected
+ * utility of the recommendation step (BOCF_EU_MEAN / _CLOSED / _MC); the Monte-Carlo mode reads the normals of the eu-sample upload and
+ * returns the MEAN over its S samples (not that entry point's sum); utility kind BOCF_UTIL_PROGRAM evaluates the resident program
+ * (Monte-Carlo mode).  L <= 32.  The Monte-Carlo mode takes square roots of the variances: pass BOCF_CLIP.
+ *
+ * Both work on a fitted model -- also after an append, after new targets, on a jittered and on an output-sharded fit --, are local to the
+ * context, recompute what they read from R and alpha in every call, keep their results in buffers of their own (the predict, candidate,
+ * acquisition, sample, best-so-far, reference, pending, Thompson and path state is left as it was) and synchronise once.  < 0 with the
+ * entry point's name in the error text, the context still usable: null or unfitted context (a fused inference leaves none), a host-given
+ * posterior, unknown flags, a bad group, a bad utility block. */
+int bocf_loo(bocf_ctx* ctx, int flags, double* mean_out, double* var_out, double* lpd_out, double* lpd_sum_out);
+int bocf_loo_utility(bocf_ctx* ctx, int group, int flags, int mode, int util_kind, const double* util_params, int n_util_params,
+                     const double* theta, int theta_dim, int L, double* val_out);
+
 #ifdef __cplusplus
 }
 #endif
