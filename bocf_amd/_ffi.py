@@ -87,6 +87,8 @@ SIGNATURES = {
     "bocf_get_pending_samples": (ctypes.c_int, [_ctx_p, _c_double_p]),
     "bocf_acq_pending": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int,
                                         _c_double_p, _c_double_p]),
+    "bocf_acq_joint": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int,
+                                      _c_double_p, ctypes.c_int, _c_double_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int)]),
     "bocf_set_output_constraints": (ctypes.c_int, [_ctx_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_int, ctypes.c_int]),
     "bocf_feasible_best": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int, _c_double_p, _c_ll_p]),
     "bocf_acq_mc_constrained": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int,

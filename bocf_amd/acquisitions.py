@@ -433,6 +433,91 @@ class uEI_pending(uEI_noiseless):
         return np.reshape(acqX, (X.shape[0], 1)), np.reshape(dacq_dX, X.shape)
 
 
+class uEI_joint(AcquisitionBase):
+    """Joint Monte-Carlo expected improvement of the composite utility at a whole batch of q points (q-uEI), 1 <= q <= 8: a row of X is a
+    batch, its q points side by side (length q * d), and
+
+        alpha(X) = sum_l p_l (1/S) sum_s max( max_k U(theta_l, y_s(x_k)) - best_l, 0 ),
+
+    y_s a joint posterior sample at the q points made from Z_samples[s] (S, m, q) through the Cholesky factor of the latent, noiseless
+    covariance -- the quantity CompositeGreedyBatch maximises one point at a time and the Thompson evaluators approximate.  Value and
+    gradient run on the device (bocf_acq_joint; the gradient follows the envelope rule with Z, theta and the incumbent fixed), so two
+    batches are compared under common random numbers and all q points can be improved together (CompositeJointBatch).  best_l is the
+    best-so-far of uEI_noiseless.
+
+    Random numbers, all in the constructor and in this order: W_samples (25, m) and -- without full support -- ten utility parameters, as
+    every composite acquisition draws them, then Z_samples = np.random.normal(size=(n_samples, m, q)).  update_Z_samples(n) redraws
+    Z_samples alone.  Parameter conventions are uEI_noiseless's: _compute_acq uses utility_params_samples, _compute_acq_withGradients the
+    support or ONE freshly drawn parameter per call.  The gradient form holds 128 points on the device: more batches than 128 // q are
+    worked off in groups.  Only compiled-in device utilities are accepted: anything else raises NotImplementedError."""
+    analytical_gradient_prediction = True
+    _model_entry = "acq_joint"
+    _device_refine = False        # (its objective has an entry point of its own: outside the device-resident refinement)
+
+    def __init__(self, model, space, optimizer=None, cost_withGradients=None, utility=None, q=2, n_samples=64):
+        if not 1 <= int(q) <= 8:
+            raise ValueError("q must be in 1 .. 8")
+        if not 1 <= int(n_samples) <= 256:
+            raise ValueError("n_samples must be in 1 .. 256")
+        self.optimizer = optimizer
+        self.utility = utility
+        self.q = int(q)
+        super(uEI_joint, self).__init__(model, space, optimizer, cost_withGradients=cost_withGradients)
+        self._init_composite(cost_withGradients)
+        self.Z_samples = np.random.normal(size=(int(n_samples), self.model.output_dim, self.q))
+
+    def update_Z_samples(self, n_samples):
+        n_samples = int(n_samples)
+        if not 1 <= n_samples <= 256:
+            raise ValueError("n_samples must be in 1 .. 256")
+        self.Z_samples = np.random.normal(size=(n_samples, self.model.output_dim, self.q))
+
+    def _joint_kind(self):
+        try:
+            kind = self.utility.device_kind(self.model.output_dim)
+        except NotImplementedError:
+            kind = None
+        if kind is None or kind == _ffi.UTIL_PROGRAM:
+            raise NotImplementedError("uEI_joint needs a utility with a compiled-in device kind (Utility(..., device=...): %s): the joint "
+                                      "samples and their maximum over the batch run on the device, there is no host loop and no utility program"
+                                      % ", ".join(COMPILED_IN))
+        return kind
+
+    def _batches(self, X):
+        X = np.atleast_2d(np.asarray(X, dtype=float))
+        if X.shape[1] % self.q:
+            raise ValueError("a row holds q = %d points side by side: its length must be a multiple of q" % self.q)
+        return X
+
+    def _compute_acq(self, X):
+        X = self._batches(X)
+        kind = self._joint_kind()
+        prob = self.utility_prob_dist if self.use_full_support else None
+        acqX = self._device_model().acq_joint(X, self.q, kind, self.utility.device_params, device_thetas(kind, self.utility_params_samples), prob,
+                                              self.Z_samples, n_hyps=self.n_hyps_samples)
+        return np.reshape(acqX, (X.shape[0], 1))
+
+    def _compute_acq_withGradients(self, X):
+        X = self._batches(X)
+        if self.use_full_support:
+            samples2, prob = self.utility.parameter_dist.support, self.utility_prob_dist
+        else:
+            samples2, prob = self.utility.parameter_dist.sample(1), None
+        kind = self._joint_kind()
+        thetas = device_thetas(kind, samples2)
+        model, step = self._device_model(), max(1, 128 // self.q)
+        acqX, dacq = np.empty((X.shape[0], 1)), np.empty(X.shape)
+        entry_h = getattr(model, "_current_h", None)          # a call leaves the model on the last hyper-sample: every group starts from the same one
+        for i in range(0, X.shape[0], step):
+            if i and entry_h is not None:
+                model.set_hyperparameters(entry_h)
+            a, g = model.acq_joint(X[i:i + step], self.q, kind, self.utility.device_params, thetas, prob, self.Z_samples, n_hyps=self.n_hyps_samples,
+                                   grad=True)
+            acqX[i:i + step, 0] = a
+            dacq[i:i + step] = np.reshape(g, (len(a), -1))
+        return acqX, dacq
+
+
 class uEI_constrained(uEI_noiseless):
     """uEI_noiseless under linear constraints on the outputs (constraints.OutputConstraints):
 

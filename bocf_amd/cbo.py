@@ -169,6 +169,62 @@ class CompositeGreedyBatch(object):
             acq.set_pending_points(None)
 
 
+class CompositeJointBatch(object):
+    """q <= 8 suggestions per iteration by maximising the joint Monte-Carlo expected improvement of the composite utility (q-uEI) over all
+    q points together.  `acquisition` is a bocf_amd.uEI_joint with q = batch_size.  compute_batch draws n_starting random batches, scores
+    them in one device call, keeps the n_anchor best as anchors, adds the batch of `warm_start` (any evaluator whose compute_batch returns
+    (q, d), e.g. a CompositeGreedyBatch) as one more anchor, refines all anchors together on -alpha with the batched L-BFGS-B inside the
+    bounds (lbfgsb_batched, which has no limit on the q * d dimensions; its arc search only accepts decreases of -alpha), scores the
+    refined batches again and returns the best as (q, d).  `last_info` records anchors, their values, the refined batches and theirs.
+    Draws from np.random, in this order: the starting design (samples_multidimensional_uniform over the bounds tiled q times: one
+    np.random.uniform per coordinate of a batch, q * d calls), then whatever warm_start.compute_batch draws, then -- only without full
+    support of the utility parameter -- one parameter per gradient call of the refinement."""
+
+    def __init__(self, acquisition, batch_size, n_starting=256, n_anchor=16, warm_start=None):
+        if not 1 <= int(batch_size) <= 8:
+            raise ValueError("batch_size must be in 1 .. 8")
+        if not hasattr(acquisition, "Z_samples") or getattr(acquisition, "q", None) != int(batch_size):
+            raise TypeError("CompositeJointBatch needs a bocf_amd.uEI_joint acquisition with q = batch_size")
+        if int(n_anchor) < 1 or int(n_starting) < int(n_anchor):
+            raise ValueError("1 <= n_anchor <= n_starting")
+        if warm_start is not None and not hasattr(warm_start, "compute_batch"):
+            raise TypeError("warm_start must be a batch evaluator (compute_batch)")
+        self.acquisition = acquisition
+        self.batch_size = int(batch_size)
+        self.n_starting, self.n_anchor = int(n_starting), int(n_anchor)
+        self.warm_start = warm_start
+        self.last_info = None
+
+    def compute_batch(self, duplicate_manager=None, context_manager=None, x_baseline=None):
+        acq, q = self.acquisition, self.batch_size
+        bounds = _bounds_of(acq.space) * q
+        starts = samples_multidimensional_uniform(bounds, self.n_starting)
+        values = np.asarray(acq._compute_acq(starts), dtype=float).reshape(-1)
+        anchors = starts[np.argsort(-values, kind="stable")[:self.n_anchor]]
+        if self.warm_start is not None:
+            warm = np.asarray(self.warm_start.compute_batch(duplicate_manager=duplicate_manager, context_manager=context_manager, x_baseline=x_baseline),
+                              dtype=float)
+            if warm.size != anchors.shape[1]:
+                raise ValueError("warm_start returned %r, not (q, d) = (%d, %d)" % (warm.shape, q, anchors.shape[1] // q))
+            anchors = np.vstack((anchors, warm.reshape(1, -1)))
+        lo, hi = np.array([b[0] for b in bounds]), np.array([b[1] for b in bounds])
+        anchors = np.minimum(np.maximum(anchors, lo), hi)
+        anchor_values = np.asarray(acq._compute_acq(anchors), dtype=float).reshape(-1)
+
+        def f_df(X):
+            f, g = acq.acquisition_function_withGradients(X)
+            return np.asarray(f).reshape(-1), np.asarray(g)
+        refined, _ = lbfgsb_batched(f_df, anchors, bounds)
+        refined_values = np.asarray(acq._compute_acq(refined), dtype=float).reshape(-1)
+        # the best of everything scored under the one set of parameters _compute_acq uses: a refined batch, or its start where the
+        # gradient calls saw another parameter draw
+        pool, pool_values = np.vstack((refined, anchors)), np.concatenate((refined_values, anchor_values))
+        best = int(np.argmax(pool_values))
+        self.last_info = {"anchors": anchors, "anchor_values": anchor_values, "refined": refined, "refined_values": refined_values,
+                          "value": float(pool_values[best])}
+        return pool[best].reshape(q, -1)
+
+
 def distinct_picks(idx):
     """Row s of idx ranks path s's candidates; path s takes its first candidate that no earlier path took."""
     taken = []

@@ -199,6 +199,11 @@ struct bocf_ctx {
   int pd_r = 0, pd_S = 0;    // pending points resident (0 = none) and the samples F, G were made for
   DevBuf pd_XP, pd_VP, pd_Wp, pd_muP, pd_cov, pd_pack, pd_QFG, pd_par, pd_best, pd_T, pd_muc, pd_E;
   std::vector<double> pd_host, pd_up;   // Sigma(P, P) | mu(P) as copied back; Q | F | G as uploaded (kept: the upload is asynchronous)
+  // ---- joint q-point acquisition (capi_joint.hip): V, Ky^-1 K*, mu, Sigma and the gradients of the chunk's points, the utility block with
+  // the transposed normals behind it, the incumbents (Ha, L), the per-batch pivot counts and the gradient kernel's scratch in buffers of
+  // its own.  Nothing in them outlives a call: no fit, append or candidate upload has anything to invalidate here.
+  DevBuf jt_V, jt_W, jt_mu, jt_cov, jt_dmean, jt_dvar, jt_dcov, jt_par, jt_best, jt_fl, jt_E, jt_dout;
+  std::vector<double> jt_tail;          // Z transposed (and the caller's incumbents) as the tail of util_up's block (kept: its capacity is reused)
   // ---- pathwise posterior samples (capi_paths.hip): per hyper-sample h one block omega (m', F, d) | phase (m', F) | w (m', F, S) |
   // v (m', Np, BOCF_TILE) with pt_S[h] paths of pt_F[h] features (pt_S[h] = 0: none); staging and per-call scratch of their own
   std::vector<DevBuf> pt_buf;

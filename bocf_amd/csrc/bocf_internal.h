@@ -517,6 +517,28 @@ void launch_pending_acq(const PendArgs& a, hipStream_t s);
 void launch_pending_grad(const PendArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------
+// joint Monte-Carlo expected improvement of the composite utility at q-point batches (joint.hip; the factor is joint_chol.h)
+// ---------------------------------------------------------------------------------------
+struct JointArgs {
+  const double* cov; int ldc; long strideC;         // Sigma_j between the points of the launch: (m, rows, ldc) of one hyper-sample; batch b is rows / columns b q .. b q + q - 1
+  const double* mu; int ldm;                        // mu_j of the points: (m, ldm)
+  const double* Zt;                                 // (m, q, S) transposed host normals, s fastest
+  const double* best;                               // (L) incumbent of this hyper-sample
+  const double* theta; int theta_dim; const double* prob; int L;
+  const double* util_params;                        // (BOCF_MAX_M)
+  int m, q, S, B, util_kind;
+  double* acq; int* floored; int accumulate; double scale;   // (B) each (floored may be nullptr): written, or added to (hyper-sample h > 0)
+  // gradient form
+  const double* dmu; const double* ds2; int ldg;    // d mu_j / dx, d sigma^2_j / dx: (m, ldg, d)
+  const double* dcov; int Cn;                       // d Sigma_j(x_c, x_a) / dx_c of all Cn = B q points: (m, Cn, Cn, d)
+  double* E;                                        // (B, m, q, S) scratch: written and read inside one workgroup
+  int d; double* dacq;                              // (B q, d)
+};
+void launch_joint_acq(const JointArgs& a, hipStream_t s);
+void launch_joint_grad(const JointArgs& a, hipStream_t s);
+void launch_joint_tail(double* acq, int B, int n, hipStream_t s);   // acq[B .. n) = -inf
+
+// ---------------------------------------------------------------------------------------
 // constrained Monte-Carlo expected improvement: linear output constraints inside the sample sum (cacq.hip)
 // ---------------------------------------------------------------------------------------
 #define BOCF_MAX_CONSTRAINTS 8

@@ -150,6 +150,7 @@ class multi_outputGP(object):
         self.sample_jitter_tries = 10                      # rungs of the jitter ladder of the joint posterior samples
         self.last_sample_jitter = None                     # the jitter per output of the last posterior_samples_f / thompson_topk draw
         self.last_pending_jitter = None                    # the jitter per output of the last set_pending_points
+        self.last_joint_floored = None                     # floored pivots per batch of the last acq_joint
         self._sampler_outputs = None                       # per output: parameter state of GPModel.model
         self._Ymat = None                                  # (m, N) targets, cached for the inferences of one update
         self._ibuf = None                                  # argument block of bocf_infer (arrays + ctypes pointers)
@@ -747,6 +748,46 @@ class multi_outputGP(object):
         self._begin_acq(n_hyps, False)
         self._resident_for_fit("pending", "no pending points resident for this fit: call set_pending_points")
         return self._run_acq("bocf_acq_pending", (int(util_kind),), X, util_params, thetas, prob, W, grad, fetch)
+
+    # ---- joint q-point expected improvement ------------------------------------------------------------------------------------------
+    def acq_joint(self, X, q, util_kind, util_params, thetas, prob, Z, n_hyps=None, best=None, grad=False):
+        """Joint Monte-Carlo expected improvement of the composite utility at B batches of q points, 1 <= q <= 8 (bocf_acq_joint): X is
+        (B, q, d), (B, q * d) or (B * q, d), Z (S, output_dim, q), S <= 256, the normals common to all batches and hyper-samples.  best:
+        None = the best-so-far of acq_mc (the hyper-sample current on entry), or the incumbents (L,) or (hyper-samples averaged, L).
+        Returns alpha (B,), or (alpha (B,), d alpha / dX (B, q, d)) with grad=True (B * q <= 128 then).  The number of floored pivots
+        of every batch is kept in last_joint_floored (B,); the values stay on the device for select_topk, which then ranks batches."""
+        q = int(q)
+        if not 1 <= q <= 8:
+            raise ValueError("q must be in 1 .. 8")
+        Z = _ffi.f64(Z)
+        if Z.ndim != 3 or Z.shape[1:] != (self.output_dim, q) or not 1 <= Z.shape[0] <= 256:
+            raise ValueError("Z must be (1 <= S <= 256, output_dim, q)")
+        if self._X is None:
+            raise RuntimeError("no model yet: call updateModel first")
+        d = self._X.shape[1]
+        X = _ffi.f64(X)
+        if X.size == 0 or X.size % (q * d):
+            raise ValueError("X must hold whole batches of q points: (B, q, %d), (B, q * %d) or (B * q, %d)" % (d, d, d))
+        X = X.reshape(-1, d)
+        B = X.shape[0] // q
+        if grad and X.shape[0] > 128:
+            raise ValueError("the gradient form takes at most 128 points (B * q <= 128)")
+        self._begin_acq(n_hyps, False)
+        util = self._utility_args(util_params, thetas, prob)
+        if best is not None:
+            n_h = 1 if self.fixed_hyps else (self._H if n_hyps is None else max(1, min(int(n_hyps), self._H)))
+            best = _ffi.f64(best)
+            if best.shape not in ((util[5],), (n_h, util[5])):
+                raise ValueError("best must be (L,) or (hyper-samples averaged, L) = (%d, %d)" % (n_h, util[5]))
+            best = _ffi.f64(np.broadcast_to(best, (n_h, util[5])))
+        self._set_candidates(X)
+        acq = np.empty(B)
+        dacq = np.empty((B, q, d)) if grad else None
+        floored = np.zeros(B, dtype=np.int32)
+        _ffi.check(_ffi.load().bocf_acq_joint(self._context().handle, q, _ffi.dptr(Z), Z.shape[0], int(util_kind), *util, _ffi.dptr(best), _ffi.dptr(acq),
+                                              _ffi.dptr(dacq), floored.ctypes.data_as(ctypes.POINTER(ctypes.c_int))), "bocf_acq_joint")
+        self.last_joint_floored = floored.astype(int)
+        return (acq, dacq) if grad else acq
 
     # ---- linear output constraints and the constrained Monte-Carlo acquisition ---------------------------------------------------
     def set_output_constraints(self, constraints):

@@ -487,6 +487,30 @@ int bocf_get_pending_samples(bocf_ctx* ctx, double* F_out);
 int bocf_acq_pending(bocf_ctx* ctx, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim,
                      const double* prob, int L, double* acq_out, double* dacq_out);
 
+/* ---- joint q-point expected improvement of the composite utility (q-uEI): the quantity the greedy and the Thompson
+ * batches approximate, at whole batches.  The resident candidates are read as B = C / q batches, batch b = rows b q .. b q + q - 1,
+ * 1 <= q <= 8.  Per output j of hyper-sample h and batch X = (x_1 .. x_q):
+ *   Sigma_j = k_j(X, X) - V_X^T V_X, symmetrised                       the latent, noiseless posterior covariance, as for the pending points
+ *   tau_j   = 1e-8 max(mean diag Sigma_j, 1e-10)                        rung 0 of the pending points' ladder; there are no further rungs
+ *   C_j     = row-wise Cholesky factor of Sigma_j + tau_j I with a pivot floor: p_k = a_kk - sum_{i<k} C_ki^2, and where !(p_k > 1e-10)
+ *             p_k := 1e-10 and the pivot counts as floored -- no batch can fail
+ *   y_sjk   = mu_jk + sum_{i <= k} C_j[k][i] Z[s, j, i]                 Z (S, m, q): host normals, common to all batches and hyper-samples
+ *   alpha(X) = (1/Ha) sum_h sum_l p_l (1/S) sum_s max(max_k U(theta_l, y_s.k) - best_hl, 0)
+ * best: (Ha, L) incumbents, or NULL = the best-so-far of the Monte-Carlo acquisitions per hyper-sample (option "best_group" honoured as in
+ * bocf_acq_pending).  Argument conventions of bocf_acq_pending otherwise: theta (L, theta_dim), prob (L) or NULL (= 1 / L), the first
+ * acq_hyper_samples hyper-samples are averaged, BOCF_UTIL_PROGRAM is refused.  acq_out (B) or NULL: the values also stay in the acquisition
+ * vector (entries B .. C - 1 are -inf) for the top-k selection, which then ranks batches.  floored_out (B) or NULL: floored pivots per
+ * batch, summed over outputs and hyper-samples.  dacq_out (B, q, d) or NULL: d alpha / dx of every point by the envelope rule with Z,
+ * theta, best and tau fixed, the maximising point k* being the lowest index of the maximum; a floored pivot is a constant --
+ *   dalpha/dx_a = sum_j [ mubar_ja dmu_j(x_a)/dx + Sigmabar_j[a][a] dsigma^2_j(x_a)/dx + 2 sum_{b != a} Sigmabar_j[a][b] d_1 Sigma_j(x_a, x_b) ],
+ * Sigmabar_j the reverse pass of the factorization applied to Cbar_j[k][i] = sum_s Ybar[s][j][k] Z[s, j, i].  The value form takes any B and
+ * works in chunks of whole batches (at most 512 points; V and Sigma of a chunk fit in "workspace_mb"); the gradient form takes C <= 128 in
+ * one chunk.  S <= 256, m <= 16 outputs per hyper-sample.  fp64 only, buffers of its own: the Monte-Carlo samples, the reference set, the
+ * pending points, the paths and the utility program stay resident; one stream synchronisation per call; every failure returns < 0 with the
+ * entry point's name in the error text. */
+int bocf_acq_joint(bocf_ctx* ctx, int q, const double* Z, int S, int util_kind, const double* util_params, int n_util_params, const double* theta,
+                   int theta_dim, const double* prob, int L, const double* best, double* acq_out, double* dacq_out, int* floored_out);
+
 /* ---- constrained uEI: linear constraints on the outputs inside the Monte-Carlo sum.  The simulator's outputs also
  * decide whether a design is admissible; the constraints are functions of the same m' outputs per hyper-sample the utility reads, so they
  * are applied sample by sample (the reference's AcquisitionBase has its constraint weighting commented out, base.py:5-74):
