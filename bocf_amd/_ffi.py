@@ -22,6 +22,8 @@ UTIL_LINEAR, UTIL_NEG_SQ_DIST, UTIL_NEG_SUM_EXP, UTIL_NEG_EXP_COS, UTIL_ROSENBRO
 UTIL_PROGRAM = 5        # the utility program staged on the context (bocf_set_utility_program)
 EU_MEAN, EU_CLOSED, EU_MC = 0, 1, 2
 REFINE_LINEAR, REFINE_MC = 0, 1
+RISK_QUANTILE, RISK_UPPER_TAIL, RISK_LOWER_TAIL = 0, 1, 2      # kinds of bocf_acq_risk
+RISK_MAX_SAMPLES = 4096
 # why a row of bocf_refine_acq stopped (RefineReason of csrc/refine_step.h)
 REFINE_REASONS = ("running", "pgtol", "factr", "arc_failed", "maxiter", "maxfun", "nonfinite_start", "nan_gradient")
 EU_MODES = {"mean": EU_MEAN, "closed": EU_CLOSED, "mc": EU_MC}
@@ -132,6 +134,9 @@ SIGNATURES = {
     "bocf_loo": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "bocf_loo_utility": (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p,
                                         ctypes.c_int, ctypes.c_int, _c_double_p]),
+    "bocf_acq_risk": (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p,
+                                     ctypes.c_int, _c_double_p, _c_double_p]),
+    "bocf_acq_linear_ucb": (ctypes.c_int, [_ctx_p, ctypes.c_double, _c_double_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p]),
     "bocf_get_stat": (ctypes.c_int, [_ctx_p, ctypes.c_char_p, _c_ll_p]),
     "bocf_option_count": (ctypes.c_int, []),
     "bocf_option_info": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), _c_ll_p, _c_ll_p, ctypes.POINTER(ctypes.c_int),

@@ -69,6 +69,18 @@ class AcquisitionBase(object):
             raise TypeError("bocf_amd acquisitions need a bocf_amd.multi_outputGP model (no CPU fallback)")
         return self.model
 
+    def _compiled_in_kind(self, who, why):
+        """The compiled-in device kind of the utility, for the acquisitions with an entry point of their own: they have no host loop and
+        take no utility program, so anything else is NotImplementedError -- `who` needs one because `why`."""
+        try:
+            kind = self.utility.device_kind(self.model.output_dim)
+        except NotImplementedError:
+            kind = None
+        if kind is None or kind == _ffi.UTIL_PROGRAM:
+            raise NotImplementedError("%s needs a utility with a compiled-in device kind (Utility(..., device=...): %s): %s"
+                                      % (who, ", ".join(COMPILED_IN), why))
+        return kind
+
     # -- the device-resident refinement (AcquisitionOptimizer(..., refine="device"), DESIGN.md section 19)
     _device_refine = False        # True on the classes the device loop covers
 
@@ -128,8 +140,8 @@ class _ClosedForm(AcquisitionBase):
         self.use_full_support = self.utility.parameter_dist.use_full_support
         self.n_hyps_samples = min(10, self.model.number_of_hyps_samples())
 
-    def _evaluate(self, X, n_theta_samples, entry):
-        """(X (n, d), what model.`entry` returns for it) with the support and its weights, or n_theta_samples freshly drawn thetas."""
+    def _parameters(self, n_theta_samples):
+        """(thetas (L, m), weights (L,) or None): the support and its weights, or n_theta_samples freshly drawn thetas."""
         if self.use_full_support:
             self.utility_params_samples = self.utility.parameter_dist.support
             self.utility_param_dist = np.atleast_1d(self.utility.parameter_dist.prob_dist)
@@ -137,8 +149,12 @@ class _ClosedForm(AcquisitionBase):
         else:
             self.utility_params_samples = self.utility.parameter_dist.sample(n_theta_samples)
             prob = None
+        return np.asarray(self.utility_params_samples, dtype=float).reshape(len(self.utility_params_samples), -1), prob
+
+    def _evaluate(self, X, n_theta_samples, entry):
+        """(X (n, d), what model.`entry` returns for it) with the parameters of _parameters(n_theta_samples)."""
+        thetas, prob = self._parameters(n_theta_samples)
         X = np.atleast_2d(X)
-        thetas = np.asarray(self.utility_params_samples, dtype=float).reshape(len(self.utility_params_samples), -1)
         # the h-loop of maEI.py:85-98 runs on the device (with fixed hyper-parameters its identical passes are one pass)
         return X, getattr(self._device_model(), entry)(X, self._kind, thetas, prob, n_hyps=self.n_hyps_samples)
 
@@ -391,15 +407,7 @@ class uEI_pending(uEI_noiseless):
         self.pending_points, self.pending_Z, self._staged_serial = P, Z, None
 
     def _pending_kind(self):
-        try:
-            kind = self.utility.device_kind(self.model.output_dim)
-        except NotImplementedError:
-            kind = None
-        if kind is None or kind == _ffi.UTIL_PROGRAM:
-            raise NotImplementedError("uEI_pending needs a utility with a compiled-in device kind (Utility(..., device=...): %s): the "
-                                      "conditioning on pending points runs on the device, there is no host loop and no utility program"
-                                      % ", ".join(COMPILED_IN))
-        return kind
+        return self._compiled_in_kind("uEI_pending", "the conditioning on pending points runs on the device, there is no host loop and no utility program")
 
     def _stage(self):
         model = self._device_model()
@@ -473,15 +481,7 @@ class uEI_joint(AcquisitionBase):
         self.Z_samples = np.random.normal(size=(n_samples, self.model.output_dim, self.q))
 
     def _joint_kind(self):
-        try:
-            kind = self.utility.device_kind(self.model.output_dim)
-        except NotImplementedError:
-            kind = None
-        if kind is None or kind == _ffi.UTIL_PROGRAM:
-            raise NotImplementedError("uEI_joint needs a utility with a compiled-in device kind (Utility(..., device=...): %s): the joint "
-                                      "samples and their maximum over the batch run on the device, there is no host loop and no utility program"
-                                      % ", ".join(COMPILED_IN))
-        return kind
+        return self._compiled_in_kind("uEI_joint", "the joint samples and their maximum over the batch run on the device, there is no host loop and no utility program")
 
     def _batches(self, X):
         X = np.atleast_2d(np.asarray(X, dtype=float))
@@ -542,15 +542,7 @@ class uEI_constrained(uEI_noiseless):
         self.constraints = constraints
 
     def _constrained_kind(self):
-        try:
-            kind = self.utility.device_kind(self.model.output_dim)
-        except NotImplementedError:
-            kind = None
-        if kind is None or kind == _ffi.UTIL_PROGRAM:
-            raise NotImplementedError("uEI_constrained needs a utility with a compiled-in device kind (Utility(..., device=...): %s): the "
-                                      "constraints are applied inside the device's Monte-Carlo sum, there is no host loop and no utility program"
-                                      % ", ".join(COMPILED_IN))
-        return kind
+        return self._compiled_in_kind("uEI_constrained", "the constraints are applied inside the device's Monte-Carlo sum, there is no host loop and no utility program")
 
     def _evaluate(self, X, samples, prob, grad):
         kind = self._constrained_kind()
@@ -572,6 +564,129 @@ class uEI_constrained(uEI_noiseless):
             samples2, prob = self.utility.parameter_dist.sample(1), None
         acqX, dacq_dX = self._evaluate(X, samples2, prob, True)
         return np.reshape(acqX, (X.shape[0], 1)), np.reshape(dacq_dX, X.shape)
+
+
+def risk_rank(level, n_samples):
+    """The integer rank the device takes for a level in [0, 1] and S samples: min(S - 1, floor(level * S)), computed here, once, in double
+    precision (the C ABI takes only the integer, so no floating floor is computed twice)."""
+    level, S = float(level), int(n_samples)
+    if not 0.0 <= level <= 1.0:
+        raise ValueError("level must be in [0, 1]")
+    if S < 1:
+        raise ValueError("no samples")
+    return min(S - 1, int(np.floor(level * S)))
+
+
+class _Risk(_MonteCarlo):
+    """Order statistics of the Monte-Carlo samples of the composite utility: with u_s = U(theta_l, mu(x) + sigma(x) o W_s),
+    the parent's samples, in ascending order (ties by sample index, a NaN as -inf) and k = risk_rank(level, S),
+
+        alpha(x) = sum_l p_l rho_l(x),   rho = u_(k) (uUCB) | mean of u_(0) .. u_(k) (uCVaR, lower) | mean of u_(k) .. u_(S-1) (uCVaR, upper),
+
+    averaged over the hyper-samples, on the device (bocf_acq_risk); the gradient is pathwise over the selected samples.  There is no
+    incumbent, so the acquisition is informative where uEI is flat (early in a run, or with no feasible training point).
+
+    Parameter conventions and np.random touchpoints are uEI_noiseless's: _compute_acq uses utility_params_samples (the support with its
+    weights, or the ten parameters drawn at construction), _compute_acq_withGradients the support or ONE freshly drawn parameter per call.
+    There is no host fallback and no utility program: a utility without a compiled-in device kind raises NotImplementedError."""
+    analytical_gradient_prediction = True
+    _model_entry = "acq_risk"
+    _device_refine = False        # (its objective has an entry point of its own: outside the device-resident refinement)
+    _risk_kind = _ffi.RISK_QUANTILE
+
+    def __init__(self, model, space, optimizer=None, cost_withGradients=None, utility=None, level=0.9):
+        super(_Risk, self).__init__(model, space, optimizer, cost_withGradients=cost_withGradients, utility=utility)
+        risk_rank(level, len(self.W_samples))               # (validates the level)
+        self.level = float(level)
+
+    @property
+    def rank(self):
+        """k for the current W_samples."""
+        return risk_rank(self.level, len(self.W_samples))
+
+    def _risk_device_kind(self):
+        return self._compiled_in_kind(type(self).__name__, "the samples are ranked on the device, there is no host loop and no utility program")
+
+    def _evaluate(self, X, samples, prob, grad):
+        kind = self._risk_device_kind()
+        if len(self.W_samples) > _ffi.RISK_MAX_SAMPLES:
+            raise ValueError("at most %d Monte-Carlo samples (W_samples)" % _ffi.RISK_MAX_SAMPLES)
+        return self._device_model().acq_risk(X, self._risk_kind, self.rank, kind, self.utility.device_params, device_thetas(kind, samples), prob,
+                                             W=self.W_samples, n_hyps=self.n_hyps_samples, grad=grad)
+
+    def _compute_acq(self, X, parallel=True):
+        X = np.atleast_2d(X)
+        prob = self.utility_prob_dist if self.use_full_support else None
+        return np.reshape(self._evaluate(X, self.utility_params_samples, prob, False), (X.shape[0], 1))
+
+    def _compute_acq_withGradients(self, X):
+        X = np.atleast_2d(X)
+        if self.use_full_support:
+            samples2, prob = self.utility.parameter_dist.support, self.utility_prob_dist
+        else:
+            samples2, prob = self.utility.parameter_dist.sample(1), None
+        acqX, dacq_dX = self._evaluate(X, samples2, prob, True)
+        return np.reshape(acqX, (X.shape[0], 1)), np.reshape(dacq_dX, X.shape)
+
+
+class uUCB(_Risk):
+    """Upper confidence bound of the composite utility: the `level` quantile of its Monte-Carlo samples, u_(k) with
+    k = min(S - 1, floor(level * S)) -- an exact order statistic, no interpolation.  See _Risk."""
+    _risk_kind = _ffi.RISK_QUANTILE
+
+
+class uCVaR(_Risk):
+    """Tail mean of the composite utility's Monte-Carlo samples with k = min(S - 1, floor(level * S)): tail="lower" is the mean of the
+    k + 1 worst samples u_(0) .. u_(k) (the conditional value at risk at `level`: a point that is good even when things go badly),
+    tail="upper" the mean of the S - k best, u_(k) .. u_(S-1).  See _Risk."""
+
+    def __init__(self, model, space, optimizer=None, cost_withGradients=None, utility=None, level=0.1, tail="lower"):
+        if tail not in ("lower", "upper"):
+            raise ValueError("tail must be 'lower' or 'upper'")
+        super(uCVaR, self).__init__(model, space, optimizer, cost_withGradients=cost_withGradients, utility=utility, level=level)
+        self.tail = tail
+        self._risk_kind = _ffi.RISK_LOWER_TAIL if tail == "lower" else _ffi.RISK_UPPER_TAIL
+
+
+class maUCB(_ClosedForm):
+    """Confidence bound of a linear utility theta . f(x) in closed form (GP-UCB; GPyOpt's AcquisitionLCB with the sign of a maximiser):
+
+        alpha(x) = sum_l p_l [ theta_l . mu(x) + exploration_weight * sqrt(sum_j theta_lj^2 var_j(x)) ],
+
+    averaged over the hyper-samples, value and gradient on the device (bocf_acq_linear_ucb).  Needs a linear utility.  The utility
+    parameters are maEI's: the support with its weights, or three freshly drawn ones per call."""
+    _model_entry = "acq_linear_ucb"
+    _device_refine = False        # (its objective has an entry point of its own: outside the device-resident refinement)
+
+    def __init__(self, model, space, optimizer=None, cost_withGradients=None, utility=None, exploration_weight=2):
+        super(maUCB, self).__init__(model, space, optimizer, cost_withGradients=cost_withGradients, utility=utility)
+        if not np.isfinite(exploration_weight):
+            raise ValueError("exploration_weight must be finite")
+        self.exploration_weight = float(exploration_weight)
+
+    def _ucb(self, X, grad):
+        if not getattr(self.utility, "linear", False) and getattr(self.utility, "device", None) != "linear":
+            raise NotImplementedError("%s is the closed form of a LINEAR utility (Utility(..., linear=True) or Utility(..., device='linear')); "
+                                      "for any other compiled-in utility use uUCB" % type(self).__name__)
+        thetas, prob = self._parameters(3)
+        X = np.atleast_2d(X)
+        return X, self._device_model().acq_linear_ucb(X, self.exploration_weight, thetas, prob, n_hyps=self.n_hyps_samples, grad=grad)
+
+    def _compute_acq(self, X):
+        X, acqX = self._ucb(X, False)
+        return np.reshape(acqX, (X.shape[0], 1))
+
+    def _compute_acq_withGradients(self, X):
+        X, (acqX, dacq_dX) = self._ucb(X, True)
+        return np.reshape(acqX, (X.shape[0], 1)), np.reshape(dacq_dX, X.shape)
+
+
+class UCB(maUCB):
+    """Single-output specialisation of maUCB (n_hyps_samples = 1, as EI)."""
+
+    def __init__(self, *a, **kw):
+        super(UCB, self).__init__(*a, **kw)
+        self.n_hyps_samples = 1
 
 
 class uPI(_MonteCarlo):

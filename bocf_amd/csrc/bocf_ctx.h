@@ -229,6 +229,9 @@ struct bocf_ctx {
   // from R and alpha, so no fit, append or target update has anything to invalidate here.
   DevBuf loo_out, loo_sum, loo_shift, loo_par, loo_rows, loo_val;
   std::vector<double> loo_shift_host;   // source of the shift's upload (kept: the copy is asynchronous)
+  // ---- quantile / tail-mean and confidence-bound acquisitions (capi_risk.hip): theta | prob | utility parameters of a call in a buffer of
+  // its own -- the parameter and best-so-far caches of the improvement acquisitions are left as they were.  Nothing in it outlives a call.
+  DevBuf rk_par;
   UtilPack util_up;         // host source of the utility block's upload (util_args.h says why it lives here); kg_par, pd_par, cq_par are its device copies
 };
 

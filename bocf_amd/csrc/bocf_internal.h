@@ -581,6 +581,25 @@ struct CeuArgs {
   double scale, pscale;                             // of G: n_hyps with one resident hyper-sample, else 1; of P: 1 / (n_h S)
 };
 void launch_ceu(const CeuArgs& a, bool grad, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------
+// quantile / tail-mean acquisitions of the composite utility and the closed-form confidence bound (risk.hip)
+// ---------------------------------------------------------------------------------------
+struct RiskArgs {
+  const double* mean; const double* var; long ld;   // (m, ld) rows of one hyper-sample, first C columns valid
+  const double* dmean; const double* dvar; long ldg; int d;   // gradient form: (m, ldg, d)
+  int m, C, L, S;
+  int kind, rank;                                   // BOCF_RISK_*, the integer rank k in [0, S - 1]
+  int util_kind, theta_dim;
+  const double* theta; const double* prob;          // device (L, theta_dim), (L)
+  const double* util_params;                        // (BOCF_MAX_M)
+  const double* Wt;                                 // (m, S) transposed common random numbers
+  double kappa;                                     // the closed form's exploration weight (launch_linear_ucb only)
+  double* acq; double* dacq;                        // (C), (C, d)
+  int accumulate; double scale;                     // written, or added to (hyper-sample h > 0); 1 / H
+};
+void launch_risk(const RiskArgs& a, bool grad, hipStream_t s);
+void launch_linear_ucb(const RiskArgs& a, bool grad, hipStream_t s);
 // min_out[l], max_out[l] = min / max over the N training points of U(theta_l, mu(X_i)): one workgroup per parameter, fixed order
 void launch_train_utility_range(const double* mu_train, int N, int m, int util_kind, const double* theta, int theta_dim, int L, const double* util_params,
                                 double* min_out, double* max_out, hipStream_t s);

@@ -838,6 +838,28 @@ class multi_outputGP(object):
         self._constraints_resident()
         return self._run_acq("bocf_acq_mc_constrained", (int(util_kind),), X, util_params, thetas, prob, W, grad, fetch)
 
+    # ---- quantile / tail-mean acquisitions of the composite utility and the closed-form confidence bound -------
+    def acq_risk(self, X, kind, rank, util_kind, util_params, thetas, prob, W=None, n_hyps=None, grad=False, fetch=True):
+        """Order statistic of the Monte-Carlo samples of the composite utility over the batch X (n, d) (bocf_acq_risk): with the samples
+        u_s = U(theta_l, mu + sigma o W_s) in ascending order (ties by sample index, NaN as -inf), `kind` _ffi.RISK_QUANTILE is u_(rank),
+        _ffi.RISK_UPPER_TAIL the mean of u_(rank) .. u_(S-1), _ffi.RISK_LOWER_TAIL the mean of u_(0) .. u_(rank); 0 <= rank <= S - 1 is an
+        integer (the caller turns a level into it), S <= 4096.  Conventions of acq_mc: W (S, output_dim) are the common random numbers;
+        there is no incumbent.  Returns alpha (n,), or (alpha (n,), d alpha / dX (n, d)) with grad=True (pathwise over the selected
+        samples).  The values stay on the device for select_topk (fetch=False returns None)."""
+        self._begin_acq(n_hyps, False)
+        return self._run_acq("bocf_acq_risk", (int(kind), int(rank), int(util_kind)), X, util_params, thetas, prob, W, grad, fetch)
+
+    def acq_linear_ucb(self, X, kappa, thetas, prob, n_hyps=None, grad=False, fetch=True):
+        """Closed-form confidence bound of theta . f over the batch X (n, d) (bocf_acq_linear_ucb):
+        sum_l p_l [theta_l . mu + kappa sqrt(sum_j theta_lj^2 var_j)], averaged over the hyper-samples; thetas (L, output_dim).  Returns
+        alpha (n,), or (alpha (n,), d alpha / dX (n, d)) with grad=True.  The values stay on the device for select_topk."""
+        self._begin_acq(n_hyps, False)
+        thetas = _ffi.f64(np.atleast_2d(thetas))
+        if thetas.shape[1] != self.output_dim:
+            raise ValueError("theta must have output_dim entries")
+        prob = None if prob is None else _ffi.f64(np.atleast_1d(prob))
+        return self._call_acq("bocf_acq_linear_ucb", lambda: (float(kappa), _ffi.dptr(thetas), _ffi.dptr(prob), thetas.shape[0]), X, None, grad, fetch)
+
     # ---- joint posterior and composite Thompson sampling ------------------------------------------------------------------------
     def _group(self):
         """Device group of the current hyper-sample (bocf_posterior_cov / bocf_posterior_samples)."""
@@ -1118,15 +1140,22 @@ class multi_outputGP(object):
         """The tail the acquisition entry points share: W (S, output_dim) goes up when given, X (n, d) becomes the resident candidates,
         then `name`(handle, *head, the utility block, *tail(), acq, dacq) runs unless n = 0 (`tail` checks and returns the arguments
         behind the block).  Returns acq (n,) (None with fetch=False), or (acq, dacq (n, d)) with grad=True."""
+        def middle():
+            extra = tail() if tail else ()
+            return (*head, *self._utility_args(util_params, thetas, prob), *extra)
+        return self._call_acq(name, middle, X, W, grad, fetch)
+
+    def _call_acq(self, name, middle, X, W, grad, fetch):
+        """W (S, output_dim) goes up when given, X (n, d) becomes the resident candidates, then `name`(handle, *middle(), acq, dacq) runs
+        unless n = 0.  Returns acq (n,) (None with fetch=False), or (acq, dacq (n, d)) with grad=True."""
         if W is not None:
             self.set_mc_samples(W)
         n = self._set_candidates(np.atleast_2d(X))
-        extra = tail() if tail else ()
-        util = self._utility_args(util_params, thetas, prob)
+        args = middle()
         acq = np.empty(n) if fetch else None
         dacq = np.empty((n, self._X.shape[1])) if grad else None
         if n:
-            _ffi.check(getattr(_ffi.load(), name)(self._context().handle, *head, *util, *extra, _ffi.dptr(acq), _ffi.dptr(dacq)), name)
+            _ffi.check(getattr(_ffi.load(), name)(self._context().handle, *args, _ffi.dptr(acq), _ffi.dptr(dacq)), name)
         return (acq, dacq) if grad else acq
 
     REFINE_POLL_EVERY = 8      # passes between two reads of the running-rows word (the sweep is in DESIGN.md section 19)

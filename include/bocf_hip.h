@@ -702,6 +702,41 @@ int bocf_loo(bocf_ctx* ctx, int flags, double* mean_out, double* var_out, double
 int bocf_loo_utility(bocf_ctx* ctx, int group, int flags, int mode, int util_kind, const double* util_params, int n_util_params,
                      const double* theta, int theta_dim, int L, double* val_out);
 
+/* ---- quantile and tail-mean acquisitions of the composite utility.  U o f is not Gaussian, so a confidence bound or a
+ * risk measure of U(theta, f(x)) has no closed form; the estimator is an order statistic of the Monte-Carlo samples uEI already draws.
+ * Per candidate x, hyper-sample and utility parameter theta_l:
+ *   u_s      = U(theta_l, mu(x) + sigma(x) o W_s),  s = 0 .. S - 1      mu, sigma exactly the posterior bocf_acq_mc reads (variance with noise,
+ *                                                                      clipped at 1e-10), W the resident samples of bocf_set_mc_samples
+ *   order    : by value ascending, then by sample index ascending; a NaN utility ranks -- and counts -- as -inf (the convention of the
+ *              top-k kernels), and -0.0 is +0.0 (equal as numbers: the index decides between them)
+ *   u_(k)    = the sample with exactly k samples before it in that order, s*(k) its index, k an integer rank in [0, S - 1]
+ *   rho      = u_(k)                                   BOCF_RISK_QUANTILE
+ *            = mean of u_(k) .. u_(S-1), S - k terms    BOCF_RISK_UPPER_TAIL
+ *            = mean of u_(0) .. u_(k),   k + 1 terms    BOCF_RISK_LOWER_TAIL   (the conditional value at risk)
+ *   alpha(x) = (1/Ha) sum_h sum_l p_l rho_hl(x)         hyper-sample loop of bocf_acq_mc (options acq_hyper_samples); prob NULL = 1 / L
+ * The caller turns a level beta into the rank; the ABI takes the integer only, so no floating floor is computed twice.  The gradient is
+ * pathwise over the selected set T ({s*(k)} for the quantile, the tail's index set for the tail kinds):
+ *   d rho / dx_q = (1/|T|) sum_{s in T} sum_j dU/dy_j(y_s) (dmu_j/dx_q + W_sj / (2 sigma_j) dsigma^2_j/dx_q)
+ * -- the per-sample term bocf_acq_mc_grad accumulates for improving samples.  There is no incumbent: option best_group is not read and the
+ * best-so-far cache of the improvement acquisitions is left as it was.  The selection is exact (no interpolation between order statistics)
+ * and independent of how the samples are spread over the hardware.  S <= 4096.
+ *
+ * bocf_acq_risk: alpha of every resident candidate into acq_out (C) or NULL -- the values are left as the context's acquisition vector, so
+ *   bocf_select_topk and bocf_global_topk work on them; dacq_out (C, d) or NULL = value only.  BOCF_UTIL_PROGRAM is refused; the gradient
+ *   form is refused on a bocf_set_posterior context and for d > 64.
+ * bocf_acq_linear_ucb: the closed form for the linear utility theta^T f (GP-UCB; GPyOpt's AcquisitionLCB with the sign of a maximiser),
+ *   alpha(x) = (1/Ha) sum_h sum_l p_l [ theta_l^T mu + kappa sqrt(sum_j theta_lj^2 var_j) ],
+ *   d alpha / dx_q: theta^T dmu/dx_q + kappa (sum_j theta_j^2 dvar_j/dx_q) / (2 sqrt(sum_j theta_j^2 var_j));
+ *   theta (L, m'), m' the outputs per hyper-sample; kappa finite (kappa = 0 is theta^T mu, negative kappa the lower bound).
+ * fp64.  One stream, one synchronisation per call.  Every failure returns < 0 with the entry point's name in the error text: unfitted model,
+ * no resident samples, rank outside [0, S - 1], unknown kind, S > 4096, a utility program, a bad utility block, d > 64 with gradients, a
+ * non-finite kappa; the checks that need no context run before it is touched. */
+enum { BOCF_RISK_QUANTILE = 0, BOCF_RISK_UPPER_TAIL = 1, BOCF_RISK_LOWER_TAIL = 2 };
+#define BOCF_RISK_MAX_SAMPLES 4096
+int bocf_acq_risk(bocf_ctx* ctx, int kind, int rank, int util_kind, const double* util_params, int n_util_params, const double* theta,
+                  int theta_dim, const double* prob, int L, double* acq_out, double* dacq_out);
+int bocf_acq_linear_ucb(bocf_ctx* ctx, double kappa, const double* theta, const double* prob, int L, double* acq_out, double* dacq_out);
+
 #ifdef __cplusplus
 }
 #endif
