@@ -53,6 +53,7 @@ SIGNATURES = {
     "bocf_set_kernel_ids": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
     "bocf_update_targets": (ctypes.c_int, [_ctx_p, _c_double_p, _c_double_p]),
     "bocf_append": (ctypes.c_int, [_ctx_p, _c_double_p, _c_double_p, _c_double_p]),
+    "bocf_remove": (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, _c_double_p]),
     "bocf_lml_gradients": (ctypes.c_int, [_ctx_p, _c_double_p, _c_double_p, _c_double_p]),
     "bocf_infer": (ctypes.c_int, [_ctx_p, _c_double_p, _c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_double_p,
                                   _c_double_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),

@@ -270,10 +270,14 @@ class CBO(object):
     recommended designs maximise the constrained expected utility (recommend.current_marginal_argmaxes), an infeasible outcome worth
     infeasible_utility (a scalar or one value per utility parameter; default: the lowest utility of the posterior mean at the training
     points), and a recommendation whose TRUE outputs violate constraints.feasible is scored with that worth in
-    historical_optimal_values.  last_recommendation carries pof, the smoothed probability of feasibility at the recommended points."""
+    historical_optimal_values.  last_recommendation carries pof, the smoothed probability of feasibility at the recommended points.
+    max_observations: a sliding window -- once the data exceed it the loop forgets one observation per acquisition before the model update
+    (forget="oldest": index 0; or a callable forget(X, Y) -> index); at least 2; None (default) keeps every observation.  A window sets
+    model.incremental_remove = True ON THE MODEL PASSED IN, so that its updateModel takes the delete-and-add update on the resident factor."""
 
     def __init__(self, model, space, objective, acquisition, evaluator, X_init, Y_init=None, cost=None, normalize_Y=False,
-                 model_update_interval=1, expectation_utility=None, constraints=None, infeasible_utility=None):
+                 model_update_interval=1, expectation_utility=None, constraints=None, infeasible_utility=None, max_observations=None,
+                 forget="oldest"):
         if cost is not None:
             raise NotImplementedError("only a constant evaluation cost is supported (cost=None)")
         self.model = model
@@ -291,6 +295,14 @@ class CBO(object):
         self.normalize_Y = normalize_Y
         self.cost = _ConstantCost()
         self.model_update_interval = model_update_interval
+        if max_observations is not None and int(max_observations) < 2:
+            raise ValueError("max_observations must be at least 2 (or None: keep every observation)")
+        if forget != "oldest" and not callable(forget):
+            raise ValueError("forget is 'oldest' or a callable forget(X, Y) -> index")
+        self.max_observations = None if max_observations is None else int(max_observations)
+        self.forget = forget
+        if self.max_observations is not None and hasattr(model, "incremental_remove"):
+            model.incremental_remove = True      # the window's delete-and-add update runs on the resident factor
         self.historical_optimal_values = []
         self.historical_time = []
         self.n_attributes = self.model.output_dim
@@ -423,6 +435,7 @@ class CBO(object):
             pass
         self.X = np.vstack((self.X, self.suggested_sample))
         self.evaluate_objective()
+        self._forget_observations()
         if self.num_acquisitions % self.model_update_interval == 0:
             self._update_model()
         self.model.get_model_parameters_names()
@@ -441,6 +454,19 @@ class CBO(object):
         self.Y_new, cost = self.objective.evaluate_w_noise(self.suggested_sample)
         self.cost.update_cost_model(self.suggested_sample, cost)
         self.Y = [np.vstack((old, new)) for old, new in zip(self.Y, self.Y_new)]
+
+    def _forget_observations(self):
+        """Sliding window (max_observations): while the data exceed it, one observation leaves -- index 0 (forget="oldest") or the one
+        the callable forget(X, Y) names.  With one suggestion per acquisition that is one row per iteration, which the model update
+        that follows takes as a removal and an append on the resident factor, O(N^2), instead of a refit."""
+        if getattr(self, "max_observations", None) is None:        # (a loop object built without __init__ has no window either)
+            return
+        while self.X.shape[0] > self.max_observations:
+            k = 0 if self.forget == "oldest" else int(self.forget(self.X, self.Y))
+            if not -self.X.shape[0] <= k < self.X.shape[0]:
+                raise IndexError("forget returned %d for %d observations" % (k, self.X.shape[0]))
+            self.X = np.delete(self.X, k, axis=0)
+            self.Y = [np.delete(y, k, axis=0) for y in self.Y]
 
     def _distance_last_evaluations(self):
         return float(np.linalg.norm(self.X[-1] - self.X[-2]))

@@ -224,6 +224,12 @@ void launch_loo_rows(int* rows, int N, int L, hipStream_t s);
 void launch_append_write(double* S, double* R, double* RT, long strideS, double* E, double* ET, long strideE, int Np, int N,
                          const double* u, const double* w, const double* sumsq, long ldsumsq, const KernHyp* hyp, int* fail, int m,
                          hipStream_t s);
+// Removal of observation k (remove.hip): U' -> S (both halves), R' -> R, R^T, E, E^T through the T scratch (Np x Np per output), row / column
+// N-1 back to identity padding.  coef: 2 Np doubles per output, part: 2 (Np / 128) Np doubles per output.
+void launch_remove_factor(double* S, double* R, double* RT, double* T, long strideS, double* E, double* ET, long strideE, int Np, int N, int k,
+                          double* coef, double* part, int m, hipStream_t s);
+// rows k+1 .. N-1 of nblk row-major (rows, d) blocks (stride apart) move up by one; tmp: nblk (N - 1 - k) d doubles
+void launch_remove_rows(double* buf, long stride, int nblk, int N, int k, int d, double* tmp, hipStream_t s);
 
 // d lml / d (variance, lengthscale_q, noise) per output from alpha and Kinv (upper tiles valid):
 // part: (m, nblocks, 2 + d) scratch; out: (m, 2 + d) = [dvariance, dnoise, dls_0 ... dls_{d-1}]

@@ -1,5 +1,5 @@
 // Fit-side entry points of the C ABI (include/bocf_hip.h): data staging, alpha / refinement, bocf_fit (+ output-sharded form),
-// bocf_update_targets, bocf_append, bocf_lml_gradients, bocf_infer, bocf_hmc and the inspection hooks.  The factorization schedules are
+// bocf_update_targets, bocf_append, bocf_remove, bocf_lml_gradients, bocf_infer, bocf_hmc and the inspection hooks.  The factorization schedules are
 // capi_chol.hip, the context / options / predict / acquisition side is capi.hip.
 #include "bocf_ctx.h"
 
@@ -643,6 +643,60 @@ extern "C" int bocf_append(bocf_ctx* c, const double* x_new, const double* Y, do
   c->N = N + 1;
   if (c->mu_train.ensure(sizeof(double) * (size_t)m * c->N)) return -1;
   return refresh_targets(c, Y, lml_out);
+}
+
+// One observation fewer by plane rotations of the resident factor (remove.hip) instead of a refit.  Returns 1 -- the caller
+// refits, nothing has been touched -- when an output carries jitter or the fit is output-sharded.  There is no pivot test: the new
+// diagonal is a hypot of existing entries.  The freed row N-1 is identity padding again, so a bocf_append can follow at every N.
+// Everything derived from the N-point factor is dropped (factor_changed).  One host synchronisation: the targets go up through the pinned
+// arena, the kernels, the alpha solve and the log-marginal's copy queue behind them.
+// Covered by tests/test_gpu_remove.py.
+extern "C" int bocf_remove(bocf_ctx* c, int index, const double* Y, double* lml_out) {
+  if (!c || !c->fitted || c->canned || !Y) return fail("bocf_remove", "model not fitted / null Y");
+  if (index < 0 || index >= c->N) return fail("bocf_remove", "index outside [0, N)");
+  if (c->N < 2) return fail("bocf_remove", "the only observation cannot be removed");
+  if (c->sharded) return 1;                              // an output-sharded fit keeps no upper factor to rotate: the caller refits
+  for (int j = 0; j < c->m; ++j)
+    if (c->jitter[j] != 0.0) return 1;                   // a jittered factor is not shrunk (the ladder decides from scratch)
+  HIPCHK(hipSetDevice(c->device));
+  const int N = c->N, Np = c->Np, m = c->m, d = c->d, nb = Np / BOCF_TILE;
+  const long strideS = (long)Np * Np, strideE = (long)nb * BOCF_TILE * BOCF_TILE;
+  // scratch: the rotation coefficients (Vs), the block partial sums (meanpart), the rows of X / Xs on the move (Kstar) -- the predict
+  // pass's workspaces, as in bocf_append -- and the T scratch for the factor (the Ky^-1 an inference left there is dropped below)
+  if (c->Vs.ensure(sizeof(double) * (size_t)2 * m * Np) || c->meanpart.ensure(sizeof(double) * (size_t)2 * m * nb * Np) ||
+      c->Kstar.ensure(sizeof(double) * (size_t)(m + 1) * Np * d) || c->T.ensure(sizeof(double) * strideS * m))
+    return -1;
+  factor_changed(c);
+  c->C = 0;                                              // the resident candidate batch is replaced
+  const std::vector<double> yc = centre_targets(c, Y, N - 1, Np, m);
+  const size_t bH = ((sizeof(KernHyp) * m + 63) / 64) * 64, bY = sizeof(double) * (size_t)m * Np;
+  char* ar = fit_arena(c, 0, bH + bY);
+  if (ar) {
+    memcpy(ar, c->hyp.data(), sizeof(KernHyp) * m);
+    memcpy(ar + bH, yc.data(), bY);
+  }
+  // (without the arena the sources are c->hyp and yc, both alive until the synchronisation below)
+  HIPCHK(hipMemcpyAsync(c->hypd.p, ar ? static_cast<const void*>(ar) : static_cast<const void*>(c->hyp.data()), sizeof(KernHyp) * m,
+                        hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->yc.p, ar ? static_cast<const void*>(ar + bH) : static_cast<const void*>(yc.data()), bY, hipMemcpyHostToDevice,
+                        c->stream));
+  c->arena_used = 0;
+  {
+    PhaseTimer t(c, "remove");
+    launch_remove_factor(c->S.as<double>(), c->R.as<double>(), c->RT.as<double>(), c->T.as<double>(), strideS, c->E.as<double>(),
+                         c->ET.as<double>(), strideE, Np, N, index, c->Vs.as<double>(), c->meanpart.as<double>(), m, c->stream);
+    launch_remove_rows(c->X.as<double>(), 0, 1, N, index, d, c->Kstar.as<double>(), c->stream);
+    launch_remove_rows(c->Xs.as<double>(), c->xs_stride, m, N, index, d, c->Kstar.as<double>() + (size_t)Np * d, c->stream);
+  }
+  c->N = N - 1;
+  {
+    PhaseTimer t(c, "remove_alpha");
+    if (solve_alpha(c, true)) return -1;
+  }
+  if (lml_out) HIPCHK(hipMemcpyAsync(lml_out, c->lml.p, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  LAUNCHCHK();
+  return 0;
 }
 
 // the launches of bocf_lml_gradients: Ky^-1 = R R^T (upper tiles, into the T scratch) and the hyper-gradient sums -> c->gout (m, 2 + d)

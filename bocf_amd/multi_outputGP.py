@@ -91,6 +91,27 @@ class _OutputView(object):
         return self._p.predict(self._p._X)[0][self._j].min()
 
 
+def match_removed_row(prevX, X):
+    """How X follows from prevX by deleting ONE row: (k, False) when X is prevX without row k, (k, True) when X is prevX without row k
+    plus one new last row, None for every other change (the caller refits).  With duplicate rows several k describe the same X: the
+    smallest is returned.  Pure NumPy: no device, no model state."""
+    prevX, X = np.asarray(prevX), np.asarray(X)
+    if prevX.ndim != 2 or X.ndim != 2 or prevX.shape[1] != X.shape[1] or prevX.shape[0] < 2:
+        return None
+    n = prevX.shape[0]
+    if X.shape[0] == n - 1:
+        kept, appended = X, False
+    elif X.shape[0] == n:
+        kept, appended = X[:-1], True
+    else:
+        return None
+    differs = np.flatnonzero(np.any(prevX[:-1] != kept, axis=1))
+    k = int(differs[0]) if differs.size else n - 1
+    if not np.array_equal(prevX[k + 1:], kept[k:]):
+        return None
+    return k, appended
+
+
 class multi_outputGP(object):
     """
     General class for handling a multi-output Gaussian process (drop-in for multi_outputGP.py:9).
@@ -138,6 +159,10 @@ class multi_outputGP(object):
         self._fit_key = None
         self._cov_points = self._next_point = self._grad_point = None
         self.incremental = True       # O(N^2) updateModel when only targets change or one observation is appended
+        # ... and, on request, when one row of X was deleted (with or without one new last row): bocf_remove (+ bocf_append).  Off by default:
+        # an updateModel with fewer rows is a refit, as it always was (the jitter ladder and the schedule start afresh);
+        # remove_observations needs no switch, CBO(max_observations=...) sets it on its model
+        self.incremental_remove = False
         # ---- hyper-parameter learning (fixed_hyps=False): GPModel's sampler settings (gpmodel.py:32)
         self.n_burnin, self.subsample_interval, self.step_size, self.leapfrog_steps, self.max_iters = 100, 10, 1e-1, 20, 200
         # a leapfrog trajectory whose Ky stops factorizing: "raise" = the reference (LinAlgError out of jitchol propagates out of
@@ -224,7 +249,65 @@ class multi_outputGP(object):
                     self.log_marginal = lml
                     self._fit_serial += 1
                     return
+            elif self.incremental_remove:
+                # one row deleted (an outlier dropped, a sliding window), possibly with one new last row: O(N^2) as well
+                hit = match_removed_row(prevX, X)
+                if hit is not None and self._remove_then_append(hit[0], X, Y, Ymat, hit[1], lml):
+                    self.log_marginal = lml
+                    self._fit_serial += 1
+                    return
         self._fit()
+
+    def _remove_then_append(self, k, X, Y, Ymat, appended, lml):
+        """bocf_remove of row k of the resident inputs, then (appended) bocf_append of X's last row.  False: the device asked for a refit."""
+        lib, ctx = _ffi.load(), self._context()
+        Yrem = Ymat if not appended else _ffi.f64(np.stack([y[:-1] for y in Y], 0))      # the targets of the rows that stay
+        if _ffi.check(lib.bocf_remove(ctx.handle, int(k), _ffi.dptr(Yrem), _ffi.dptr(lml)), "bocf_remove") != 0:
+            return False
+        if not appended:
+            return True
+        xnew = _ffi.f64(X[-1])
+        rc = _ffi.check(lib.bocf_append(ctx.handle, _ffi.dptr(xnew), _ffi.dptr(Ymat), _ffi.dptr(lml)), "bocf_append")
+        if rc != 0:
+            self._fitted = False                 # the device holds the model without row k and without the new row: refit
+        return rc == 0
+
+    def remove_observations(self, indices):
+        """Removes the observations `indices` (rows of the training inputs) from the model: from the highest index down, one bocf_remove
+        each -- O(N^2) per row on the resident factor -- or one refit of what remains when the device refuses (a jittered factor, an
+        output-sharded fit) or no fixed-hyper-parameter fit is resident."""
+        if self._X is None:
+            raise RuntimeError("updateModel has not been called")
+        N = self._X.shape[0]
+        idx = sorted({int(i) + (N if int(i) < 0 else 0) for i in np.atleast_1d(indices)}, reverse=True)
+        if not idx:
+            return
+        if idx[0] >= N or idx[-1] < 0:
+            raise IndexError("observation index out of range")
+        if len(idx) >= N:
+            raise ValueError("at least one observation must remain")
+        self._resident.forget("candidates", "reference", "pending", "paths")      # as every model change (updateModel)
+        self._Ymat = None
+        self._ibuf = None
+        if not self.fixed_hyps:
+            self._X, self._Y = np.delete(self._X, idx, axis=0), [np.delete(y, idx, axis=0) for y in self._Y]
+            return self._update_hyper_samples()
+        resident = self.incremental and self._fitted and self._hyper_key() == self._fit_key
+        lib, ctx = _ffi.load(), self._context()
+        lml = np.zeros(self.output_dim)
+        for k in idx:
+            self._X, self._Y = _ffi.f64(np.delete(self._X, k, axis=0)), [np.delete(y, k, axis=0) for y in self._Y]
+            if resident:
+                Ymat = _ffi.f64(np.stack([y[:, 0] for y in self._Y], 0))
+                try:
+                    resident = _ffi.check(lib.bocf_remove(ctx.handle, k, _ffi.dptr(Ymat), _ffi.dptr(lml)), "bocf_remove") == 0
+                except Exception:
+                    self._fitted = False         # the host arrays are ahead of the device model: the next use refits
+                    raise
+        if not resident:
+            return self._fit()
+        self.log_marginal = lml
+        self._fit_serial += 1
 
     def _hyper_key(self):
         kids, var, ls, noise = self._hyper_arrays()

@@ -181,6 +181,15 @@ int bocf_update_targets(bocf_ctx* ctx, const double* Y, double* lml_out);
  * and the inverse of Ky an inference left for bocf_lml_gradients (which is then formed anew). */
 int bocf_append(bocf_ctx* ctx, const double* x_new, const double* Y, double* lml_out);
 
+/* Removal of ONE observation, row `index` of the resident inputs, with the complete new targets Y (m,N-1): the
+ * plane rotations that row `index` of R fixes take U and R to the factor of the remaining N-1 points in O(N^2)
+ * (orthogonal transformations only; no pivot can fail).  The inputs behind `index` move up by one and row N-1
+ * becomes identity padding again, so a bocf_append can follow at every N.  Returns 0 on success; 1 when the
+ * caller must run bocf_fit instead and nothing has been touched (a jittered factor; an output-sharded fit);
+ * < 0 with bocf_last_error (not fitted, null Y, index outside [0,N), N = 1).  On success everything derived from
+ * the old factor is dropped, exactly as after bocf_append.  One host synchronisation. */
+int bocf_remove(bocf_ctx* ctx, int index, const double* Y, double* lml_out);
+
 /* Gradients of the log marginal likelihood of the CURRENT fit w.r.t. the raw hyper-parameters: kernel variance
  * (m), lengthscales (m,d) (an isotropic kernel's single gradient is the sum over d), noise variance (m).  The
  * numerical core of hyper-parameter learning (GP.parameters_changed, GPy/core/gp.py:256-258): dL_dK and
