@@ -2,7 +2,7 @@
 reference's multi_outputGP / AcquisitionBase plug-in surface.  See DESIGN.md."""
 from . import _ffi, kern, utility_program  # noqa: F401
 from .acquisition_optimizer import AcquisitionOptimizer, Design_space  # noqa: F401
-from .acquisitions import EI, PI, UCB, AcquisitionBase, maEI, maPI, maUCB, uCVaR, uEI_constrained, uEI_joint, uEI_noiseless, uEI_pending, uKG, uPI, uUCB  # noqa: F401
+from .acquisitions import EI, PI, UCB, AcquisitionBase, LogEI, maEI, maLogEI, maPI, maUCB, uCVaR, uLogEI, uEI_constrained, uEI_joint, uEI_noiseless, uEI_pending, uKG, uPI, uUCB  # noqa: F401
 from .constraints import OutputConstraints  # noqa: F401
 from .cbo import CBO, CompositeGreedyBatch, CompositeJointBatch, CompositePathwiseThompsonBatch, CompositeThompsonBatch, Sequential  # noqa: F401
 from .multi_outputGP import multi_outputGP  # noqa: F401

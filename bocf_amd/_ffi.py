@@ -138,6 +138,9 @@ SIGNATURES = {
     "bocf_acq_risk": (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p,
                                      ctypes.c_int, _c_double_p, _c_double_p]),
     "bocf_acq_linear_ucb": (ctypes.c_int, [_ctx_p, ctypes.c_double, _c_double_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p]),
+    "bocf_acq_log_linear": (ctypes.c_int, [_ctx_p, _c_double_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p]),
+    "bocf_acq_log_mc": (ctypes.c_int, [_ctx_p, ctypes.c_double, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p,
+                                       ctypes.c_int, _c_double_p, _c_double_p]),
     "bocf_get_stat": (ctypes.c_int, [_ctx_p, ctypes.c_char_p, _c_ll_p]),
     "bocf_option_count": (ctypes.c_int, []),
     "bocf_option_info": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), _c_ll_p, _c_ll_p, ctypes.POINTER(ctypes.c_int),

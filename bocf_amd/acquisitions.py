@@ -689,6 +689,88 @@ class UCB(maUCB):
         self.n_hyps_samples = 1
 
 
+class maLogEI(_ClosedForm):
+    """log of maEI in closed form (Ament et al. 2023): with z = (theta_l . mu - best_l) / sigma_l,
+
+        log alpha(x) = LSE over hyper-samples h and parameters l of [ log p_l - log H + log sigma_l + log h(z) ],   h(z) = phi(z) + z Phi(z),
+
+    value and gradient on the device (bocf_acq_log_linear), log h accurate for every finite z.  It has maEI's maximisers, but where the
+    incumbent is hard to beat -- maEI and its gradient are then exactly zero -- it stays finite with a useful gradient, so the anchor
+    selection and the refinement do not work on a plateau.  Constructor, utility parameters and np.random touchpoints are maEI's: the
+    support with its weights, or three freshly drawn parameters per call."""
+    _model_entry = "acq_log_linear"
+    _device_refine = False        # (its objective has an entry point of its own: outside the device-resident refinement)
+    _n_theta_samples = 3
+
+    def _log_ei(self, X, grad):
+        thetas, prob = self._parameters(3 if grad else self._n_theta_samples)
+        X = np.atleast_2d(X)
+        return X, self._device_model().acq_log_linear(X, thetas, prob, n_hyps=self.n_hyps_samples, grad=grad)
+
+    def _compute_acq(self, X):
+        X, acqX = self._log_ei(X, False)
+        return np.reshape(acqX, (X.shape[0], 1))
+
+    def _compute_acq_withGradients(self, X):
+        X, (acqX, dacq_dX) = self._log_ei(X, True)
+        return np.reshape(acqX, (X.shape[0], 1)), np.reshape(dacq_dX, X.shape)
+
+
+class LogEI(maLogEI):
+    """Single-output specialisation of maLogEI (n_hyps_samples = 1, as EI)."""
+
+    def __init__(self, *a, **kw):
+        super(LogEI, self).__init__(*a, **kw)
+        self.n_hyps_samples = 1
+
+
+class uLogEI(_MonteCarlo):
+    """log of a smooth surrogate of uEI_noiseless (Ament et al. 2023): with the parent's samples
+    y_s = mu(x) + sigma(x) o W_s and t = (U(theta_l, y_s) - best_l) / tau,
+
+        log alpha_tau(x) = LSE over hyper-samples h, parameters l and samples s of [ log p_l - log(H S) + log tau + log psi(t) ],
+        psi(t) = softplus(t) + 0.1 / (1 + t^2),
+
+    value and pathwise gradient on the device (bocf_acq_log_mc).  psi replaces the hinge max(t, 0) by a monotone function with a fat tail,
+    so a candidate none of whose samples improves still has a finite value and a non-zero gradient.  `tau` is in the UNITS OF THE UTILITY:
+    0 < exp(log alpha_tau) - uEI <= tau (ln 2 + 0.1), so choose it small against the improvements that matter (the default 1e-6 suits
+    utilities of order one).  Constructor draws, parameter conventions and np.random touchpoints are uEI_noiseless's.  Compiled-in utilities
+    and utility programs (Utility(..., device="program")); there is no host fallback: a host callable raises NotImplementedError."""
+    analytical_gradient_prediction = True
+    _model_entry = "acq_log_mc"
+    _device_refine = False        # (its objective has an entry point of its own: outside the device-resident refinement)
+
+    def __init__(self, model, space, optimizer=None, cost_withGradients=None, utility=None, tau=1e-6):
+        super(uLogEI, self).__init__(model, space, optimizer, cost_withGradients=cost_withGradients, utility=utility)
+        if not (np.isfinite(tau) and tau > 0):
+            raise ValueError("tau must be finite and > 0 (it is in the units of the utility)")
+        self.tau = float(tau)
+
+    def _evaluate(self, X, samples, prob, grad):
+        try:
+            kind = self.utility.device_kind(self.model.output_dim)
+        except NotImplementedError:
+            raise NotImplementedError("uLogEI needs a device utility (Utility(..., device=...): %s, or device='program' to trace a callable): the "
+                                      "log-sum-exp over the samples runs on the device, there is no host loop" % ", ".join(COMPILED_IN))
+        return self._device_model().acq_log_mc(X, kind, self.utility.device_params, device_thetas(kind, samples), prob, self.tau, W=self.W_samples,
+                                               n_hyps=self.n_hyps_samples, grad=grad,
+                                               program=self.utility.program_blob if kind == _ffi.UTIL_PROGRAM else None)
+
+    def _compute_acq(self, X, parallel=True):
+        X = np.atleast_2d(X)
+        prob = self.utility_prob_dist if self.use_full_support else None
+        return np.reshape(self._evaluate(X, self.utility_params_samples, prob, False), (X.shape[0], 1))
+
+    def _compute_acq_withGradients(self, X):
+        X = np.atleast_2d(X)
+        if self.use_full_support:
+            samples2, prob = self.utility.parameter_dist.support, self.utility_prob_dist
+        else:
+            samples2, prob = self.utility.parameter_dist.sample(1), None
+        acqX, dacq_dX = self._evaluate(X, samples2, prob, True)
+        return np.reshape(acqX, (X.shape[0], 1)), np.reshape(dacq_dX, X.shape)
+
+
 class uPI(_MonteCarlo):
     analytical_gradient_prediction = False
     _kind = _ffi.ACQ_PI

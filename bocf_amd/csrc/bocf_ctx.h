@@ -232,6 +232,10 @@ struct bocf_ctx {
   // ---- quantile / tail-mean and confidence-bound acquisitions (capi_risk.hip): theta | prob | utility parameters of a call in a buffer of
   // its own -- the parameter and best-so-far caches of the improvement acquisitions are left as they were.  Nothing in it outlives a call.
   DevBuf rk_par;
+  // ---- log-space expected improvement (capi_logei.hip): theta | prob | utility parameters of a call and the incumbents (hyper-samples
+  // averaged, L) in buffers of their own -- the parameter and best-so-far caches of the improvement acquisitions are left as they were.
+  // Nothing in them outlives a call.
+  DevBuf lg_par, lg_best;
   UtilPack util_up;         // host source of the utility block's upload (util_args.h says why it lives here); kg_par, pd_par, cq_par are its device copies
 };
 

@@ -117,7 +117,7 @@ extern "C" void bocf_destroy(bocf_ctx* c) {
                     &c->cq_tab, &c->cq_par, &c->cq_best, &c->cq_nf, &c->cu_par, &c->cu_val, &c->cu_pof, &c->cu_grad, &c->cu_rng, &c->rf_dbl, &c->rf_int, &c->rf_x2, &c->rf_acq,
                     &c->loo_out, &c->loo_sum, &c->loo_shift, &c->loo_par, &c->loo_rows, &c->loo_val,
                     &c->jt_V, &c->jt_W, &c->jt_mu, &c->jt_cov, &c->jt_dmean, &c->jt_dvar, &c->jt_dcov, &c->jt_par, &c->jt_best, &c->jt_fl, &c->jt_E, &c->jt_dout,
-                    &c->rk_par};
+                    &c->rk_par, &c->lg_par, &c->lg_best};
   for (DevBuf* b : bufs) b->release();
   if (c->infer_out) (void)hipHostFree(c->infer_out);
   if (c->tile_ctr) (void)hipFree(c->tile_ctr);

@@ -943,6 +943,32 @@ class multi_outputGP(object):
         prob = None if prob is None else _ffi.f64(np.atleast_1d(prob))
         return self._call_acq("bocf_acq_linear_ucb", lambda: (float(kappa), _ffi.dptr(thetas), _ffi.dptr(prob), thetas.shape[0]), X, None, grad, fetch)
 
+    # ---- log-space expected improvement --------------------------------------------------------------------------
+    def acq_log_linear(self, X, thetas, prob, n_hyps=None, grad=False, fetch=True):
+        """log EI of theta . f over the batch X (n, d) in closed form (bocf_acq_log_linear): the log-sum-exp over the hyper-samples and
+        the parameters of log p_l - log H + log sigma + log h(z), h(z) = phi(z) + z Phi(z), with acq_linear's posterior and incumbents
+        (each hyper-sample's own); thetas (L, output_dim).  Finite and with a useful gradient where acq_linear returns an exact 0.
+        Returns log alpha (n,), or (log alpha (n,), d log alpha / dX (n, d)) with grad=True.  The values stay on the device for
+        select_topk (fetch=False returns None)."""
+        self._begin_acq(n_hyps, True)
+        thetas = _ffi.f64(np.atleast_2d(thetas))
+        if thetas.shape[1] != self.output_dim:
+            raise ValueError("theta must have output_dim entries")
+        prob = None if prob is None else _ffi.f64(np.atleast_1d(prob))
+        return self._call_acq("bocf_acq_log_linear", lambda: (_ffi.dptr(thetas), _ffi.dptr(prob), thetas.shape[0]), X, None, grad, fetch)
+
+    def acq_log_mc(self, X, util_kind, util_params, thetas, prob, tau, W=None, n_hyps=None, grad=False, program=None, fetch=True):
+        """Log of the smooth surrogate of the Monte-Carlo EI of a device utility over the batch X (n, d) (bocf_acq_log_mc): the
+        log-sum-exp over hyper-samples, parameters and samples of log p_l - log(H S) + log tau + log psi((U - best_l) / tau),
+        psi(t) = softplus(t) + 0.1 / (1 + t^2), with acq_mc's posterior, samples W (S, output_dim) and incumbents (the hyper-sample
+        current on entry).  `tau` > 0 is in the units of the utility: exp(result) exceeds acq_mc's EI by at most tau (ln 2 + 0.1).
+        `program`: the blob for utility kind UTIL_PROGRAM.  Returns log alpha (n,), or (log alpha (n,), d log alpha / dX (n, d)) with
+        grad=True (pathwise).  The values stay on the device for select_topk (fetch=False returns None)."""
+        self._begin_acq(n_hyps, False)
+        if util_kind == _ffi.UTIL_PROGRAM:
+            self.set_utility_program(program)
+        return self._run_acq("bocf_acq_log_mc", (float(tau), int(util_kind)), X, util_params, thetas, prob, W, grad, fetch)
+
     # ---- joint posterior and composite Thompson sampling ------------------------------------------------------------------------
     def _group(self):
         """Device group of the current hyper-sample (bocf_posterior_cov / bocf_posterior_samples)."""

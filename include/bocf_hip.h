@@ -746,6 +746,40 @@ int bocf_acq_risk(bocf_ctx* ctx, int kind, int rank, int util_kind, const double
                   int theta_dim, const double* prob, int L, double* acq_out, double* dacq_out);
 int bocf_acq_linear_ucb(bocf_ctx* ctx, double kappa, const double* theta, const double* prob, int L, double* acq_out, double* dacq_out);
 
+/* ---- log-space expected improvement (Ament et al. 2023, "Unexpected Improvements to Expected Improvement").  Where the
+ * incumbent is hard to beat, EI and its gradient are exactly zero in floating point and a selection or a refinement works on a plateau;
+ * these forms have EI's maximisers but are finite with a useful gradient everywhere.  The incumbents best_l, the posterior (variance with
+ * noise, clipped at 1e-10), the hyper-sample loop (options acq_hyper_samples, best_group) and the weights p_l (1 / L when prob is NULL) are
+ * exactly those of bocf_acq_linear / bocf_acq_mc; H is the number of hyper-samples the loop walks.
+ *
+ * bocf_acq_log_linear: the closed form for the linear utility theta^T f, theta (L, m'), m' the outputs per hyper-sample.  Per (h, l):
+ *   mu = theta_l^T mu_h,  sigma = sqrt(sum_j theta_lj^2 var_hj),  z = (mu - best_l) / sigma   (no floor on sigma, in value and gradient alike)
+ *   l_lh = log sigma + log h(z),  h(z) = phi(z) + z Phi(z)
+ *   log alpha(x) = LSE_(h, l) [ log p_l - log H + l_lh ]
+ *   d log alpha  = sum_(h, l) w_lh (dsigma / sigma + r(z) (dmu - z dsigma) / sigma),  r = Phi / h, w_lh the softmax weights
+ *   log h and r are accurate for every finite z: for z <= -1 through erfcx, from |z| = 30 on through the asymptotic series of 1 - |z| Phi / phi.
+ *   A term with p_l = 0 or sigma = 0 is -inf and carries no weight; if every term is -inf the value is -inf and the gradient 0, never NaN.
+ *
+ * bocf_acq_log_mc: the Monte-Carlo form for a composite utility (compiled-in kinds and BOCF_UTIL_PROGRAM), samples y_hs = mu_h + sigma_h o W_s
+ *   of the resident normals (bocf_set_mc_samples), temperature tau > 0 in the units of the utility:
+ *   t = (U(theta_l, y_hs) - best_l) / tau,  psi(t) = softplus(t) + 0.1 / (1 + t^2)
+ *   log alpha_tau(x) = LSE_(h, l, s) [ log p_l - log(H S) + log tau + log psi(t) ]
+ *   psi is monotone and its logarithm finite for every finite t; 0 < psi(t) - max(t, 0) <= ln 2 + 0.1, so
+ *   0 < exp(log alpha_tau) - alpha_EI <= tau (ln 2 + 0.1) with alpha_EI what bocf_acq_mc returns.  The gradient is pathwise through y, the
+ *   per-sample weight being the softmax weight times psi'(t) / (tau psi(t)) times dU/dy_j.  A sample whose utility is NaN or infinite
+ *   carries no weight.
+ *
+ * Both: log alpha of every resident candidate into acq_out (C) or NULL -- the values are left as the context's acquisition vector, so
+ * bocf_select_topk and bocf_global_topk work on them; dacq_out (C, d) or NULL = value only.  The sums run in a fixed order: a candidate's bits
+ * do not depend on its batch.  Parameters and incumbents live in buffers of their own: a bocf_acq_linear / bocf_acq_mc call after one of
+ * these returns the bits it returns without it.  fp64.  One stream, one synchronisation per call.  Every failure returns < 0 with the
+ * entry point's name in the error text: unfitted model, tau not finite or <= 0, unknown utility kind, no resident samples, L outside
+ * 1 .. 32, a bad utility block, no or a mismatching resident program, no candidates, a gradient on a bocf_set_posterior context or for
+ * d > 64; the checks that need no context run before it is touched. */
+int bocf_acq_log_linear(bocf_ctx* ctx, const double* theta, const double* prob, int L, double* acq_out, double* dacq_out);
+int bocf_acq_log_mc(bocf_ctx* ctx, double tau, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim,
+                    const double* prob, int L, double* acq_out, double* dacq_out);
+
 #ifdef __cplusplus
 }
 #endif
