@@ -211,6 +211,9 @@ class multi_outputGP(object):
 
     def set_option(self, name, value):
         self._context().set_option(name, value)
+        # the host copies of the last all-hyper-sample queries were made under the old options (predict_f32 / predict_i8 choose the
+        # arithmetic of the variances): the next query goes to the device
+        self._resident.forget("query", "gradient")
         if name in ("shard_fit", "shard_fit_simulate") and value:
             # an output-sharded fit exchanges the inverse factors only: the O(N^2) incremental updates need the upper factor,
             # which stays on its owner, so every updateModel is a (sharded) refit
