@@ -1,6 +1,7 @@
 // Context of one GPU (opaque bocf_ctx of include/bocf_hip.h) and the error plumbing shared by capi.hip and comm.hip.
 #pragma once
 #include "bocf_internal.h"
+#include "call_args.h"
 #include "chol_plan.h"
 #include "predict_plan.h"
 #include "../../include/bocf_hip.h"
@@ -41,8 +42,6 @@ static inline int nsplit_for(int Np, int Cpad, int m) {
   if (ns > maxs) ns = maxs;
   return ns;
 }
-
-
 
 static_assert(PLAN_TILE == BOCF_TILE && PLAN_SMALL_N == BOCF_SMALL_N && PLAN_I8_SLICES == BOCF_I8_SLICES, "predict_plan.h mirrors bocf_internal.h");
 
@@ -263,28 +262,49 @@ int bocf_kg_stage(bocf_ctx* c, const double* Xdev, int na, int nap, double* VA, 
 int bocf_kg_chunk_size(const bocf_ctx* c, int mg);      // candidates per chunk under option workspace_mb; below 128: refuse
 int bocf_kg_chunk(bocf_ctx* c, const KgRefSet& ref, int j0, int mg, int c0, int cn, int cnp, bool with_grad, double* mu);
 int bocf_kg_chunk_dcov(bocf_ctx* c, const KgRefSet& ref, int j0, int mg, int c0, int cn, int a0, int an);
-// capi_thompson.hip, shared with capi_kg.hip: the argument checks of the joint-posterior entry points (errors name `who`) and
-// V = R^T K(X, Xq) for the mg outputs from j0 (Np x npad per output, k-major) with, for mu != nullptr, the posterior mean at Xq (mg x npad)
-int bocf_check_posterior(bocf_ctx* c, const char* who);
-int bocf_group_range(bocf_ctx* c, const char* who, int group, int* j0, int* mg, int* per);
+// capi_thompson.hip, shared with capi_kg.hip: V = R^T K(X, Xq) for the mg outputs from j0 (Np x npad per output, k-major) with, for
+// mu != nullptr, the posterior mean at Xq (mg x npad)
 int bocf_enqueue_V(bocf_ctx* c, int j0, int mg, const double* Xq, int n, int npad, double* V, double* mu);
-// capi.hip, shared with capi_constrained.hip: the posterior the Monte-Carlo acquisitions read (variance with noise, clipped at 1e-10; with
-// grad its input gradients) of every resident candidate, through the predict pass's plan and chunking; and two device vectors to the host
-// with ONE synchronisation (either may be empty)
+// capi.hip: the posterior the Monte-Carlo acquisitions read (variance with noise, clipped at 1e-10; with grad its input gradients) of every
+// resident candidate, through the predict pass's plan and chunking
 int bocf_acq_posterior(bocf_ctx* c, bool grad);
 // ... and the one bocf_expected_utility reads (predict_noiseless: no likelihood noise, clipped at 1e-10)
 int bocf_eu_posterior(bocf_ctx* c, bool grad);
+// two device vectors to the host with ONE synchronisation (either may be empty)
 int bocf_copy_pair_out(bocf_ctx* c, const void* src0, double* out0, size_t b0, const void* src1, double* out1, size_t b1);
-// capi.hip, shared with capi_refine.hip: the argument checks of bocf_acq_linear_grad / bocf_acq_mc_grad (outputs per hyper-sample, or -1;
-// errors name `who`), their parameter upload (skipped when nothing changed; *uploaded is set when it ran: one synchronisation), the part of
-// them that only enqueues -- the posterior with its gradients and one acquisition launch per hyper-sample, into c->acq / c->dacq -- and one
-// device word to the host with ONE synchronisation
-int bocf_acq_group_size(bocf_ctx* c, const char* who);
-int bocf_acq_mc_group_size(bocf_ctx* c, const char* who, int util_kind, const double* util_params, int n_util_params, int theta_dim);
-int bocf_acq_upload_params(bocf_ctx* c, const double* theta, int theta_dim, const double* prob, int L, const double* params, int nparams, bool* uploaded);
-int bocf_acq_grad_enqueue(bocf_ctx* c, int m, bool linear, int kind, int util_kind, int n_util_params, int theta_dim, int L);
+// what ends an acquisition over the resident candidates: c->acq stands for the selections, and the values (C) and gradients (C, d; either
+// may be null) go to the host with ONE synchronisation
+int bocf_acq_finish(bocf_ctx* c, double* acq_out, double* dacq_out);
+// capi.hip, shared with capi_refine.hip: the parameter upload of bocf_acq_linear[_grad] / bocf_acq_mc[_grad] (it checks L, theta and the
+// parameter count; skipped when nothing changed; *uploaded, when given, is set when it ran: one synchronisation), the part of them that
+// only enqueues -- the posterior (with grad: and its gradients) and one acquisition launch per hyper-sample, into c->acq / c->dacq; the
+// Monte-Carlo gradient form is BOCF_ACQ_EI -- and one device word to the host with ONE synchronisation
+int bocf_acq_upload_params(bocf_ctx* c, const double* theta, int theta_dim, const double* prob, int L, const double* params, int nparams,
+                           bool* uploaded = nullptr);
+int bocf_acq_enqueue(bocf_ctx* c, int m, bool linear, bool grad, int kind, int util_kind, int n_util_params, int theta_dim, int L);
 int bocf_copy_word_out(bocf_ctx* c, const int* dev, int* out);
 
+// ---- what the entry points that evaluate a utility over the posterior share (call_args.h has their checks) ----------------------------------
+// the plain record the checks read, on the caller's stack; a null context is all zeros: not fitted
+static inline CallState bocf_call_state(const bocf_ctx* c) {
+  if (!c) return CallState{};
+  return CallState{c->fitted, c->canned, c->N, c->d, c->m, c->hyper_samples, c->best_group, c->C, c->S_mc, c->eu_S, c->eu_L, c->eu_m,
+                   c->cq_K, c->cq_m, c->kg_na, c->pd_r, c->pd_S};
+}
+// The reference's h-loop (maEI.py:85-97, uEI_noiseless.py:71-82): hyper-sample h reads rows [h m, (h + 1) m) of the posterior of the resident
+// candidates -- a->mean / a->var, leading dimension pred_cap, and with grad a->dmean / a->dvar (d values per column)
+template <typename Args> static inline void bocf_posterior_rows(const bocf_ctx* c, int h, int m, bool grad, Args* a) {
+  const size_t off = (size_t)h * m * c->pred_cap;
+  a->mean = c->mean.as<double>() + off; a->var = c->var.as<double>() + off;
+  if (grad) { a->dmean = c->dmean.as<double>() + off * c->d; a->dvar = c->dvar.as<double>() + off * c->d; }
+}
+// A packed utility block (util_args.h; its host source is c->util_up) into the calling path's OWN parameter buffer, asynchronously: the
+// parameter and best-so-far caches of the improvement acquisitions are left as they were
+static inline int bocf_upload_util(bocf_ctx* c, const UtilPack& pk, DevBuf* par) {
+  if (par->ensure(pk.bytes())) return -1;
+  HIPCHK(hipMemcpyAsync(par->p, pk.host.data(), pk.bytes(), hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
 
 // HIP-event bracket of a named phase on the context's stream (only with option "profile" = 1; otherwise free)
 struct PhaseTimer {

@@ -584,8 +584,8 @@ extern "C" int bocf_mean_at_train(bocf_ctx* c, double* out) {
 }
 
 // (uploaded, when given: set when the parameters went up, which costs one stream synchronisation)
-static int upload_acq_params(bocf_ctx* c, const double* theta, int theta_dim, const double* prob, int L, const double* params, int nparams,
-                             bool* uploaded = nullptr) {
+int bocf_acq_upload_params(bocf_ctx* c, const double* theta, int theta_dim, const double* prob, int L, const double* params, int nparams,
+                           bool* uploaded) {
   if (L < 1 || L > BOCF_MAX_L) return fail("acquisition", "L out of range (1..32)");
   std::vector<double> th((size_t)L * (theta_dim > 0 ? theta_dim : 1), 0.0), pr(L), pa(BOCF_MAX_M, 0.0);
   if (theta_dim > 0) {
@@ -617,17 +617,8 @@ static int upload_acq_params(bocf_ctx* c, const double* theta, int theta_dim, co
   return 0;
 }
 
-// outputs per hyper-sample; -1 (with the error set) when the fit does not hold H whole groups
-static int group_size(bocf_ctx* c, const char* where) {
-  const int H = c->hyper_samples;
-  if (c->m % H != 0) return fail(where, "the fitted outputs are not a multiple of option hyper_samples"), -1;
-  if (c->best_group >= H) return fail(where, "option best_group is not a valid hyper-sample index"), -1;
-  if (c->m / H > BOCF_MAX_M) return fail(where, "too many outputs per hyper-sample"), -1;
-  return c->m / H;
-}
-
 // two device vectors to the host: small totals through the pinned buffer -- both copies asynchronous, one synchronisation
-static int copy_pair_out(bocf_ctx* c, const void* src0, double* out0, size_t b0, const void* src1, double* out1, size_t b1) {
+int bocf_copy_pair_out(bocf_ctx* c, const void* src0, double* out0, size_t b0, const void* src1, double* out1, size_t b1) {
   if (b0 + b1 > 0 && b0 + b1 <= BOCF_PIN_BYTES && pin_ensure(&c->pin_out, &c->pin_out_cap, b0 + b1) == 0) {
     char* pin = static_cast<char*>(c->pin_out);
     if (b0) HIPCHK(hipMemcpyAsync(pin, src0, b0, hipMemcpyDeviceToHost, c->stream));
@@ -647,17 +638,18 @@ static int copy_pair_out(bocf_ctx* c, const void* src0, double* out0, size_t b0,
 
 int bocf_acq_posterior(bocf_ctx* c, bool grad) { return run_predict(c, BOCF_ADD_NOISE | BOCF_CLIP, true, grad); }
 int bocf_eu_posterior(bocf_ctx* c, bool grad) { return run_predict(c, BOCF_CLIP, true, grad); }
-int bocf_copy_pair_out(bocf_ctx* c, const void* src0, double* out0, size_t b0, const void* src1, double* out1, size_t b1) {
-  return copy_pair_out(c, src0, out0, b0, src1, out1, b1);
+int bocf_acq_finish(bocf_ctx* c, double* acq_out, double* dacq_out) {
+  c->have_acq = true;
+  const size_t b0 = acq_out ? sizeof(double) * (size_t)c->C : 0, b1 = dacq_out ? sizeof(double) * (size_t)c->C * c->d : 0;
+  return bocf_copy_pair_out(c, c->acq.p, acq_out, b0, c->dacq.p, dacq_out, b1);
 }
 
 typedef void (*AcqLaunch)(const AcqArgs& a, hipStream_t s);
 
-// The reference's h-loop (maEI.py:85-97, uEI_noiseless.py:71-82) runs here: hyper-sample h reads rows
-// [h*m, (h+1)*m) of the mean / variance / gradient buffers and adds its share (1/H) to acq (and dacq).
-static void acq_over_hyper_samples(bocf_ctx* c, AcqArgs a, int m, int linear, AcqLaunch launch) {
+// The reference's h-loop (maEI.py:85-97, uEI_noiseless.py:71-82) runs here: hyper-sample h reads its rows of the posterior
+// (bocf_posterior_rows) and adds its share (1/H) to acq (and dacq).
+static void acq_over_hyper_samples(bocf_ctx* c, AcqArgs a, int m, int linear, bool grad, AcqLaunch launch) {
   const int H = bocf_acq_hyper_count(c);
-  const double* mean = a.mean; const double* var = a.var; const double* dmean = a.dmean; const double* dvar = a.dvar;
   for (int h = 0; h < H; ++h) {
     if (h == 0 || c->best_group < 0) {
       const int gb = bocf_best_group_of(c, h);
@@ -671,9 +663,7 @@ static void acq_over_hyper_samples(bocf_ctx* c, AcqArgs a, int m, int linear, Ac
       launch_best_so_far(c->mu_train.as<double>() + (size_t)gb * m * c->N, c->N, m, linear, a.util_kind, a.theta, a.theta_dim, a.L,
                          a.util_params, c->best.as<double>(), c->stream, a.prog);
     }
-    a.mean = mean + (size_t)h * m * a.ld;
-    a.var = var + (size_t)h * m * a.ld;
-    if (dmean) { a.dmean = dmean + (size_t)h * m * a.ldg * a.d; a.dvar = dvar + (size_t)h * m * a.ldg * a.d; }
+    bocf_posterior_rows(c, h, m, grad, &a);
     a.accumulate = h > 0;
     a.scale = 1.0 / H;
     PhaseTimer t(c, "acq");
@@ -683,19 +673,20 @@ static void acq_over_hyper_samples(bocf_ctx* c, AcqArgs a, int m, int linear, Ac
 
 // The part of an acquisition that only enqueues, with the parameters already on the device: the posterior -- with its input gradients
 // for the _grad forms -- of every resident candidate and one launch per hyper-sample; c->acq (and c->dacq) hold the result once the stream
-// gets there.  Shared by run_acq and, once per pass, by the device-resident refinement (capi_refine.hip).
-static int acq_enqueue(bocf_ctx* c, int m, bool linear, bool grad, AcqLaunch launch, int kind, int util_kind, int n_util_params, int theta_dim, int L) {
+// gets there.  Shared by run_acq and, once per pass, by the device-resident refinement (capi_refine.hip; declared in bocf_ctx.h).
+int bocf_acq_enqueue(bocf_ctx* c, int m, bool linear, bool grad, int kind, int util_kind, int n_util_params, int theta_dim, int L) {
+  const AcqLaunch launch = linear ? (grad ? launch_acq_linear_grad : launch_acq_linear) : (grad ? launch_acq_mc_grad : launch_acq_mc);
   // model.predict (maEI.py:87) / posterior_mean + posterior_variance (uEI_noiseless.py:73-74)
   if (run_predict(c, BOCF_ADD_NOISE | BOCF_CLIP, true, grad)) return -1;
   AcqArgs a{};
-  a.mean = c->mean.as<double>(); a.var = c->var.as<double>(); a.ld = c->pred_cap;
+  a.ld = c->pred_cap;
   a.m = m; a.C = c->C; a.L = L; a.kind = kind; a.util_kind = util_kind; a.theta_dim = theta_dim > 0 ? theta_dim : 1;
   a.theta = c->theta.as<double>(); a.prob = c->prob.as<double>(); a.best = c->best.as<double>();
   a.util_params = c->params.as<double>(); a.n_util_params = n_util_params; a.acq = c->acq.as<double>();
   a.prog = &c->prog;
   if (!linear) { a.Wt = c->Wt.as<double>(); a.S = c->S_mc; }
-  if (grad) { a.dmean = c->dmean.as<double>(); a.dvar = c->dvar.as<double>(); a.ldg = c->pred_cap; a.d = c->d; a.dacq = c->dacq.as<double>(); }
-  acq_over_hyper_samples(c, a, m, linear ? 1 : 0, launch);
+  if (grad) { a.ldg = c->pred_cap; a.d = c->d; a.dacq = c->dacq.as<double>(); }
+  acq_over_hyper_samples(c, a, m, linear ? 1 : 0, grad, launch);
   c->have_acq = true;
   return 0;
 }
@@ -703,38 +694,32 @@ static int acq_enqueue(bocf_ctx* c, int m, bool linear, bool grad, AcqLaunch lau
 // What the four acquisitions share once their arguments are checked: the parameters go up (only when they changed), the enqueue part above,
 // values (and gradients) to the host.
 // linear: the linear-utility forms (EI / PI of theta^T f); theta_dim as the caller gave it; the Monte-Carlo forms read the resident samples.
-static int run_acq(bocf_ctx* c, int m, bool linear, bool grad, AcqLaunch launch, int kind, int util_kind, const double* util_params, int n_util_params,
+static int run_acq(bocf_ctx* c, int m, bool linear, bool grad, int kind, int util_kind, const double* util_params, int n_util_params,
                    const double* theta, int theta_dim, const double* prob, int L, double* acq_out, double* dacq_out) {
   HIPCHK(hipSetDevice(c->device));
   if (c->C == 0) return 0;
-  if (upload_acq_params(c, theta, theta_dim, prob, L, util_params, n_util_params)) return -1;
-  if (acq_enqueue(c, m, linear, grad, launch, kind, util_kind, n_util_params, theta_dim, L)) return -1;
-  const size_t b0 = acq_out ? sizeof(double) * (size_t)c->C : 0, b1 = dacq_out ? sizeof(double) * (size_t)c->C * c->d : 0;
-  return copy_pair_out(c, c->acq.p, acq_out, b0, c->dacq.p, dacq_out, b1);
+  if (bocf_acq_upload_params(c, theta, theta_dim, prob, L, util_params, n_util_params)) return -1;
+  if (bocf_acq_enqueue(c, m, linear, grad, kind, util_kind, n_util_params, theta_dim, L)) return -1;
+  return bocf_acq_finish(c, acq_out, dacq_out);
 }
 
 extern "C" int bocf_acq_linear(bocf_ctx* c, int kind, const double* theta, const double* prob, int L, double* acq_out) {
-  if (!c || !c->fitted) return fail("bocf_acq_linear", "model not fitted");
-  if (kind != BOCF_ACQ_EI && kind != BOCF_ACQ_PI) return fail("bocf_acq_linear", "unknown acquisition kind");
-  const int m = group_size(c, "bocf_acq_linear");
+  const int m = bocf_acq_linear_check("bocf_acq_linear", bocf_call_state(c), kind);
   if (m < 0) return -1;
-  return run_acq(c, m, true, false, launch_acq_linear, kind, BOCF_UTIL_LINEAR, nullptr, 0, theta, m, prob, L, acq_out, nullptr);
+  return run_acq(c, m, true, false, kind, BOCF_UTIL_LINEAR, nullptr, 0, theta, m, prob, L, acq_out, nullptr);
 }
 
 extern "C" int bocf_acq_linear_grad(bocf_ctx* c, int kind, const double* theta, const double* prob, int L, double* acq_out,
                                     double* dacq_out) {
-  if (!c || !c->fitted) return fail("bocf_acq_linear_grad", "model not fitted");
-  if (kind != BOCF_ACQ_EI && kind != BOCF_ACQ_PI) return fail("bocf_acq_linear_grad", "unknown acquisition kind");
-  const int m = group_size(c, "bocf_acq_linear_grad");
+  const int m = bocf_acq_linear_check("bocf_acq_linear_grad", bocf_call_state(c), kind);
   if (m < 0) return -1;
-  return run_acq(c, m, true, true, launch_acq_linear_grad, kind, BOCF_UTIL_LINEAR, nullptr, 0, theta, m, prob, L, acq_out, dacq_out);
+  return run_acq(c, m, true, true, kind, BOCF_UTIL_LINEAR, nullptr, 0, theta, m, prob, L, acq_out, dacq_out);
 }
 
 extern "C" int bocf_set_mc_samples(bocf_ctx* c, const double* W, int S) {
-  if (!c || !c->fitted || !W || S < 1) return fail("bocf_set_mc_samples", "model not fitted / bad samples");
-  HIPCHK(hipSetDevice(c->device));
-  const int m = group_size(c, "bocf_set_mc_samples");     // W is (S, outputs per hyper-sample)
+  const int m = bocf_set_samples_check("bocf_set_mc_samples", bocf_call_state(c), W && S >= 1);     // W is (S, outputs per hyper-sample)
   if (m < 0) return -1;
+  HIPCHK(hipSetDevice(c->device));
   std::vector<double> wt((size_t)m * S);
   for (int s = 0; s < S; ++s)
     for (int j = 0; j < m; ++j) wt[(long)j * S + s] = W[(long)s * m + j];
@@ -745,50 +730,25 @@ extern "C" int bocf_set_mc_samples(bocf_ctx* c, const double* W, int S) {
   return 0;
 }
 
-// the utility checks of bocf_acq_mc and bocf_acq_mc_grad, in their order (errors name `me`): outputs per hyper-sample, or -1
-static int mc_group_size(bocf_ctx* c, const char* me, int util_kind, const double* util_params, int n_util_params, int theta_dim) {
-  if (util_kind < 0 || util_kind > BOCF_UTIL_PROGRAM) return fail(me, "unknown utility kind");
-  if (c->S_mc < 1) return fail(me, "no Monte-Carlo samples set (bocf_set_mc_samples)");
-  const int m = group_size(c, me);
-  if (m < 0) return -1;
-  if (util_kind == BOCF_UTIL_PROGRAM) return bocf_check_resident_program(c, me, m, theta_dim, n_util_params) ? -1 : m;
-  if ((util_kind == BOCF_UTIL_LINEAR || util_kind == BOCF_UTIL_NEG_SQ_DIST) && theta_dim != m) return fail(me, "theta_dim must equal m");
-  if (util_kind == BOCF_UTIL_ROSENBROCK && (theta_dim < 1 || (m & 1))) return fail(me, "rosenbrock utility needs theta_dim >= 1 and even m");
-  if (util_kind == BOCF_UTIL_NEG_EXP_COS && n_util_params != m) return fail(me, "neg_exp_cos needs m weights");
-  if (n_util_params > 0 && !util_params) return fail(me, "util_params is null");
-  return m;
-}
-
 extern "C" int bocf_acq_mc(bocf_ctx* c, int kind, int util_kind, const double* util_params, int n_util_params, const double* theta,
                            int theta_dim, const double* prob, int L, double* acq_out) {
-  if (!c || !c->fitted) return fail("bocf_acq_mc", "model not fitted");
-  if (kind != BOCF_ACQ_EI && kind != BOCF_ACQ_PI) return fail("bocf_acq_mc", "unknown acquisition kind");
-  const int m = mc_group_size(c, "bocf_acq_mc", util_kind, util_params, n_util_params, theta_dim);
-  if (m < 0) return -1;
-  return run_acq(c, m, false, false, launch_acq_mc, kind, util_kind, util_params, n_util_params, theta, theta_dim, prob, L, acq_out, nullptr);
+  static const char* who = "bocf_acq_mc";
+  bool program;
+  const int m = bocf_acq_mc_check(who, bocf_call_state(c), false, kind, UtilArgs{util_kind, util_params, n_util_params, theta, theta_dim, prob, L}, &program);
+  if (m < 0 || (program && bocf_check_resident_program(c, who, m, theta_dim, n_util_params))) return -1;
+  return run_acq(c, m, false, false, kind, util_kind, util_params, n_util_params, theta, theta_dim, prob, L, acq_out, nullptr);
 }
 
 extern "C" int bocf_acq_mc_grad(bocf_ctx* c, int util_kind, const double* util_params, int n_util_params, const double* theta,
                                 int theta_dim, const double* prob, int L, double* acq_out, double* dacq_out) {
-  if (!c || !c->fitted) return fail("bocf_acq_mc_grad", "model not fitted");
-  const int m = mc_group_size(c, "bocf_acq_mc_grad", util_kind, util_params, n_util_params, theta_dim);
-  if (m < 0) return -1;
-  if (c->d > 64) return fail("bocf_acq_mc_grad", "input dimension too large");
-  return run_acq(c, m, false, true, launch_acq_mc_grad, BOCF_ACQ_EI, util_kind, util_params, n_util_params, theta, theta_dim, prob, L, acq_out, dacq_out);
+  static const char* who = "bocf_acq_mc_grad";
+  const CallState st = bocf_call_state(c);
+  bool program;
+  const int m = bocf_acq_mc_check(who, st, true, BOCF_ACQ_EI, UtilArgs{util_kind, util_params, n_util_params, theta, theta_dim, prob, L}, &program);
+  if (m < 0 || (program && bocf_check_resident_program(c, who, m, theta_dim, n_util_params)) || bocf_check_grad_dim(who, st, true, true)) return -1;
+  return run_acq(c, m, false, true, BOCF_ACQ_EI, util_kind, util_params, n_util_params, theta, theta_dim, prob, L, acq_out, dacq_out);
 }
 
-// ---- for capi_refine.hip (declared in bocf_ctx.h): the checks, the parameter upload and the enqueue part of the gradient acquisitions
-int bocf_acq_group_size(bocf_ctx* c, const char* who) { return group_size(c, who); }
-int bocf_acq_mc_group_size(bocf_ctx* c, const char* who, int util_kind, const double* util_params, int n_util_params, int theta_dim) {
-  return mc_group_size(c, who, util_kind, util_params, n_util_params, theta_dim);
-}
-int bocf_acq_upload_params(bocf_ctx* c, const double* theta, int theta_dim, const double* prob, int L, const double* params, int nparams, bool* uploaded) {
-  return upload_acq_params(c, theta, theta_dim, prob, L, params, nparams, uploaded);
-}
-int bocf_acq_grad_enqueue(bocf_ctx* c, int m, bool linear, int kind, int util_kind, int n_util_params, int theta_dim, int L) {
-  return acq_enqueue(c, m, linear, true, linear ? launch_acq_linear_grad : launch_acq_mc_grad, linear ? kind : BOCF_ACQ_EI, util_kind, n_util_params,
-                     theta_dim, L);
-}
 // one device word to the host through the pinned buffer: ONE stream synchronisation
 int bocf_copy_word_out(bocf_ctx* c, const int* dev, int* out) {
   if (pin_ensure(&c->pin_out, &c->pin_out_cap, sizeof(int)) == 0) {
@@ -803,10 +763,9 @@ int bocf_copy_word_out(bocf_ctx* c, const int* dev, int* out) {
 }
 
 extern "C" int bocf_set_eu_samples(bocf_ctx* c, const double* Z, int L, int S) {
-  if (!c || !c->fitted || !Z || L < 1 || S < 1) return fail("bocf_set_eu_samples", "model not fitted / bad samples");
-  HIPCHK(hipSetDevice(c->device));
-  const int m = group_size(c, "bocf_set_eu_samples");     // Z is (L, S, outputs per hyper-sample)
+  const int m = bocf_set_samples_check("bocf_set_eu_samples", bocf_call_state(c), Z && L >= 1 && S >= 1);     // Z is (L, S, outputs per hyper-sample)
   if (m < 0) return -1;
+  HIPCHK(hipSetDevice(c->device));
   std::vector<double> zt((size_t)L * m * S);               // -> (L, m, S): lanes of a wave read consecutive samples
   for (int l = 0; l < L; ++l)
     for (int s = 0; s < S; ++s)
@@ -823,35 +782,15 @@ extern "C" int bocf_set_eu_samples(bocf_ctx* c, const double* Z, int L, int S) {
 extern "C" int bocf_expected_utility(bocf_ctx* c, int mode, int util_kind, const double* util_params, int n_util_params, const double* theta,
                                      int theta_dim, int L, const int* row_param, int n_hyps, double* val_out, double* grad_out) {
   const char* me = "bocf_expected_utility";
-  if (!c || !c->fitted) return fail(me, "model not fitted");
-  if (c->canned) return fail(me, "the context holds a host-given posterior (bocf_set_posterior): fit first");
-  if (mode < BOCF_EU_MEAN || mode > BOCF_EU_MC) return fail(me, "unknown mode");
-  if (util_kind < 0 || util_kind > BOCF_UTIL_PROGRAM) return fail(me, "unknown utility kind");
-  const int m = group_size(c, me);
-  if (m < 0) return -1;
-  if (L < 1 || theta_dim < 1 || !theta) return fail(me, "theta must be (L >= 1, theta_dim >= 1)");
-  if (mode == BOCF_EU_CLOSED && util_kind == BOCF_UTIL_PROGRAM)
-    return fail(me, "a utility program has no closed-form expectation (BOCF_EU_CLOSED): use the Monte-Carlo mode");
-  if (mode == BOCF_EU_MC && util_kind == BOCF_UTIL_PROGRAM && bocf_check_resident_program(c, me, m, theta_dim, n_util_params)) return -1;
-  if ((mode == BOCF_EU_MEAN || util_kind == BOCF_UTIL_LINEAR || util_kind == BOCF_UTIL_NEG_SQ_DIST) && theta_dim != m)
-    return fail(me, "theta_dim must equal m");
-  if (mode != BOCF_EU_MEAN && util_kind == BOCF_UTIL_ROSENBROCK && (m & 1)) return fail(me, "rosenbrock utility needs even m");
-  if (mode == BOCF_EU_CLOSED && (util_kind == BOCF_UTIL_LINEAR || util_kind == BOCF_UTIL_NEG_EXP_COS))
-    return fail(me, "no closed-form expectation for this utility (use the Monte-Carlo mode)");
-  if (mode == BOCF_EU_MC && util_kind == BOCF_UTIL_NEG_EXP_COS && n_util_params != m) return fail(me, "neg_exp_cos needs m weights");
-  if (n_util_params < 0 || n_util_params > BOCF_MAX_M || (n_util_params > 0 && !util_params)) return fail(me, "bad utility parameters");
-  if (mode == BOCF_EU_MC && c->eu_S < 1) return fail(me, "no Monte-Carlo samples set (bocf_set_eu_samples)");
-  if (mode == BOCF_EU_MC && c->eu_L < L) return fail(me, "fewer Monte-Carlo sample blocks than parameters");
-  if (mode == BOCF_EU_MC && c->eu_m != m) return fail(me, "the Monte-Carlo samples were set for another output count");
-  if (grad_out && c->d > 64) return fail(me, "input dimension too large");
-  if (n_hyps < 1) return fail(me, "n_hyps must be >= 1");
-  if (c->hyper_samples > 1 && n_hyps > c->hyper_samples) return fail(me, "n_hyps exceeds the resident hyper-samples");
+  const CallState st = bocf_call_state(c);
+  const UtilArgs u{util_kind, util_params, n_util_params, theta, theta_dim, nullptr, L};
+  bool program;
+  const int m = bocf_eu_check_utility(me, st, mode, u, &program);
+  if (m < 0 || (program && bocf_check_resident_program(c, me, m, theta_dim, n_util_params))) return -1;
+  const int rc = bocf_eu_check_call(me, st, mode, u, m, row_param, n_hyps, val_out, grad_out != nullptr);
+  if (rc) return rc < 0 ? -1 : 0;
   HIPCHK(hipSetDevice(c->device));
   const int C = c->C, d = c->d;
-  if (C == 0) return 0;
-  if (!val_out || !row_param) return fail(me, "null output / row_param");
-  for (int i = 0; i < C; ++i)
-    if (row_param[i] < 0 || row_param[i] >= L) return fail(me, "row_param out of range [0, L)");
   // theta | params | rows in one pinned staging buffer (free again once the previous call's copy is done)
   const size_t bt = sizeof(double) * (size_t)L * theta_dim, bp = sizeof(double) * BOCF_MAX_M, br = sizeof(int) * (size_t)C;
   if (c->eu_theta.ensure(bt + bp) || c->eu_rows.ensure(br) || c->eu_val.ensure(sizeof(double) * (size_t)C) ||
@@ -890,14 +829,12 @@ extern "C" int bocf_expected_utility(bocf_ctx* c, int mode, int util_kind, const
   a.scale = H == 1 ? (double)n_hyps : 1.0;
   a.prog = &c->prog;
   for (int h = 0; h < nh; ++h) {
-    a.mean = c->mean.as<double>() + (size_t)h * m * a.ld;
-    a.var = c->var.as<double>() + (size_t)h * m * a.ld;
-    if (need_grad) { a.dmean = c->dmean.as<double>() + (size_t)h * m * a.ldg * d; a.dvar = c->dvar.as<double>() + (size_t)h * m * a.ldg * d; }
+    bocf_posterior_rows(c, h, m, need_grad, &a);
     a.accumulate = h > 0;
     PhaseTimer t(c, "eu");
     launch_eu(a, c->stream);
   }
-  return copy_pair_out(c, c->eu_val.p, val_out, sizeof(double) * (size_t)C, c->eu_grad.p, grad_out, need_grad ? sizeof(double) * (size_t)C * d : 0);
+  return bocf_copy_pair_out(c, c->eu_val.p, val_out, sizeof(double) * (size_t)C, c->eu_grad.p, grad_out, need_grad ? sizeof(double) * (size_t)C * d : 0);
 }
 
 extern "C" int bocf_select_topk(bocf_ctx* c, int k, long long* idx_out, double* val_out) {

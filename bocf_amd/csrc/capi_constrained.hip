@@ -53,35 +53,17 @@ extern "C" int bocf_set_output_constraints(bocf_ctx* c, const double* A, const d
   return 0;
 }
 
-// the checks the two evaluating entry points share, in their order (errors name `who`): outputs per hyper-sample, or -1
-static int constrained_checks(bocf_ctx* c, const char* who, const UtilArgs& u) {
-  if (!c || !c->fitted) return fail(who, "model not fitted");
-  if (bocf_util_check_kind(who, u, "the constrained acquisition does not take a utility program (BOCF_UTIL_PROGRAM): use one of the compiled-in utilities"))
-    return -1;
-  if (c->cq_K < 1) return fail(who, "no output constraints resident (bocf_set_output_constraints)");
-  const int H = c->hyper_samples;
-  if (c->m % H) return fail(who, "the fitted outputs are not a whole number of hyper-samples (option hyper_samples)");
-  const int m = c->m / H;
-  if (m > BOCF_MAX_M) return fail(who, "more outputs per hyper-sample than the device utilities take (16)");
-  if (c->cq_m != m) return fail(who, "the resident output constraints were given for another m than the outputs per hyper-sample");
-  if (c->best_group >= H) return fail(who, "option best_group is not a valid hyper-sample index");
-  if (bocf_util_check(who, u, m, BOCF_EU_MC)) return -1;
-  return m;
-}
-
 // theta | prob | utility parameters in one upload; the incumbent buffers
 static int constrained_upload(bocf_ctx* c, const UtilArgs& u, int Ha) {
-  const UtilPack& pk = bocf_util_pack(u, nullptr, 0, &c->util_up);
-  if (c->cq_par.ensure(pk.bytes()) || c->cq_best.ensure(sizeof(double) * (size_t)Ha * u.L) || c->cq_nf.ensure(sizeof(long long) * (size_t)Ha)) return -1;
-  HIPCHK(hipMemcpyAsync(c->cq_par.p, pk.host.data(), pk.bytes(), hipMemcpyHostToDevice, c->stream));
-  return 0;
+  if (c->cq_best.ensure(sizeof(double) * (size_t)Ha * u.L) || c->cq_nf.ensure(sizeof(long long) * (size_t)Ha)) return -1;
+  return bocf_upload_util(c, bocf_util_pack(u, nullptr, 0, &c->util_up), &c->cq_par);
 }
 
 extern "C" int bocf_feasible_best(bocf_ctx* c, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim, int L,
                                   double* best_out, long long* n_feasible_out) {
   static const char* who = "bocf_feasible_best";
   const UtilArgs u{util_kind, util_params, n_util_params, theta, theta_dim, nullptr, L};
-  const int m = constrained_checks(c, who, u);
+  const int m = bocf_constrained_utility(who, bocf_call_state(c), u, true, BOCF_CACQ_NO_PROGRAM);
   if (m < 0) return -1;
   HIPCHK(hipSetDevice(c->device));
   if (constrained_upload(c, u, 1)) return -1;
@@ -104,13 +86,9 @@ extern "C" int bocf_acq_mc_constrained(bocf_ctx* c, int util_kind, const double*
                                        const double* prob, int L, double* acq_out, double* dacq_out) {
   static const char* who = "bocf_acq_mc_constrained";
   const UtilArgs u{util_kind, util_params, n_util_params, theta, theta_dim, prob, L};
-  const int m = constrained_checks(c, who, u);
-  if (m < 0) return -1;
-  if (c->S_mc < 1) return fail(who, "no Monte-Carlo samples set (bocf_set_mc_samples)");
-  if (c->C < 1) return fail(who, "no resident candidates (bocf_set_candidates)");
   const bool grad = dacq_out != nullptr;
-  if (grad && c->canned) return fail(who, "the context holds a host-given posterior (bocf_set_posterior): it carries no gradients; fit first");
-  if (grad && c->d > 64) return fail(who, "input dimension too large");
+  const int m = bocf_cacq_check(who, bocf_call_state(c), u, grad);
+  if (m < 0) return -1;
   const int Ha = bocf_acq_hyper_count(c);
   HIPCHK(hipSetDevice(c->device));
   if (constrained_upload(c, u, Ha)) return -1;
@@ -135,38 +113,25 @@ extern "C" int bocf_acq_mc_constrained(bocf_ctx* c, int util_kind, const double*
                            c->stream);
     }
     a.best = best; a.nfeas = nf;
-    a.mean = c->mean.as<double>() + (size_t)h * m * a.ld;
-    a.var = c->var.as<double>() + (size_t)h * m * a.ld;
-    if (grad) {
-      a.dmean = c->dmean.as<double>() + (size_t)h * m * a.ldg * a.d;
-      a.dvar = c->dvar.as<double>() + (size_t)h * m * a.ldg * a.d;
-    }
+    bocf_posterior_rows(c, h, m, grad, &a);
     a.accumulate = h > 0;
     if (grad) launch_cacq_grad(a, c->stream);
     else launch_cacq(a, c->stream);
   }
-  c->have_acq = true;
-  const size_t b0 = acq_out ? sizeof(double) * (size_t)c->C : 0, b1 = grad ? sizeof(double) * (size_t)c->C * c->d : 0;
-  return bocf_copy_pair_out(c, c->acq.p, acq_out, b0, c->dacq.p, dacq_out, b1);
+  return bocf_acq_finish(c, acq_out, dacq_out);
 }
 
 // ---- the feasibility-aware recommendation step ------------------------------------------------------------------------------------------
-static CeuState ceu_state(const bocf_ctx* c) {
-  if (!c) return CeuState{};
-  return CeuState{c->fitted, c->canned, c->m, c->hyper_samples, c->best_group, c->cq_K, c->cq_m, c->eu_S, c->eu_L, c->eu_m, c->d, c->C};
-}
-
 extern "C" int bocf_train_utility_range(bocf_ctx* c, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim, int L,
                                         double* min_out, double* max_out) {
   static const char* who = "bocf_train_utility_range";
   const UtilArgs u{util_kind, util_params, n_util_params, theta, theta_dim, nullptr, L};
-  const int m = bocf_ceu_check_utility(who, ceu_state(c), u, false);
+  const int m = bocf_constrained_utility(who, bocf_call_state(c), u, false, BOCF_CEU_NO_PROGRAM);
   if (m < 0) return -1;
   if (!min_out || !max_out) return fail(who, "null min_out / max_out");
   HIPCHK(hipSetDevice(c->device));
   const UtilPack& pk = bocf_util_pack(u, nullptr, 0, &c->util_up);
-  if (c->cu_par.ensure(pk.bytes()) || c->cu_rng.ensure(sizeof(double) * 2 * (size_t)L)) return -1;
-  HIPCHK(hipMemcpyAsync(c->cu_par.p, pk.host.data(), pk.bytes(), hipMemcpyHostToDevice, c->stream));
+  if (c->cu_rng.ensure(sizeof(double) * 2 * (size_t)L) || bocf_upload_util(c, pk, &c->cu_par)) return -1;
   const double* par = c->cu_par.as<double>();
   double* rng = c->cu_rng.as<double>();
   const int gb = bocf_best_group_of(c, 0);
@@ -180,8 +145,8 @@ extern "C" int bocf_expected_utility_constrained(bocf_ctx* c, int util_kind, con
                                                  double* pof_out, double* grad_out) {
   static const char* who = "bocf_expected_utility_constrained";
   const UtilArgs u{util_kind, util_params, n_util_params, theta, theta_dim, nullptr, L};
-  const CeuState st = ceu_state(c);
-  const int m = bocf_ceu_check_utility(who, st, u, true);
+  const CallState st = bocf_call_state(c);
+  const int m = bocf_constrained_utility(who, st, u, true, BOCF_CEU_NO_PROGRAM);
   if (m < 0) return -1;
   const bool grad = grad_out != nullptr;
   const int rc = bocf_ceu_check_call(who, st, u, m, u_infeasible, row_param, n_hyps, val_out, grad);
@@ -194,10 +159,9 @@ extern "C" int bocf_expected_utility_constrained(bocf_ctx* c, int util_kind, con
   memcpy(c->cu_tail.data(), u_infeasible, sizeof(double) * L);
   memcpy(c->cu_tail.data() + L, row_param, sizeof(int) * (size_t)C);
   const UtilPack& pk = bocf_util_pack(u, c->cu_tail.data(), c->cu_tail.size(), &c->util_up);
-  if (c->cu_par.ensure(pk.bytes()) || c->cu_val.ensure(sizeof(double) * (size_t)C) || c->cu_pof.ensure(sizeof(double) * (size_t)C) ||
-      (grad && c->cu_grad.ensure(sizeof(double) * (size_t)C * d)))
+  if (c->cu_val.ensure(sizeof(double) * (size_t)C) || c->cu_pof.ensure(sizeof(double) * (size_t)C) ||
+      (grad && c->cu_grad.ensure(sizeof(double) * (size_t)C * d)) || bocf_upload_util(c, pk, &c->cu_par))
     return -1;
-  HIPCHK(hipMemcpyAsync(c->cu_par.p, pk.host.data(), pk.bytes(), hipMemcpyHostToDevice, c->stream));
   if (bocf_eu_posterior(c, grad)) return -1;
   const double* par = c->cu_par.as<double>();
   const int H = c->hyper_samples;
@@ -212,9 +176,7 @@ extern "C" int bocf_expected_utility_constrained(bocf_ctx* c, int util_kind, con
   a.scale = H == 1 ? (double)n_hyps : 1.0;
   a.pscale = 1.0 / ((double)nh * (double)c->eu_S);
   for (int h = 0; h < nh; ++h) {
-    a.mean = c->mean.as<double>() + (size_t)h * m * a.ld;
-    a.var = c->var.as<double>() + (size_t)h * m * a.ld;
-    if (grad) { a.dmean = c->dmean.as<double>() + (size_t)h * m * a.ldg * d; a.dvar = c->dvar.as<double>() + (size_t)h * m * a.ldg * d; }
+    bocf_posterior_rows(c, h, m, grad, &a);
     a.accumulate = h > 0;
     PhaseTimer t(c, "ceu");
     launch_ceu(a, grad, c->stream);

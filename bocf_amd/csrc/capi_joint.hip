@@ -15,22 +15,11 @@ static const char* kWorkspace = "the joint workspace exceeds option workspace_mb
 extern "C" int bocf_acq_joint(bocf_ctx* c, int q, const double* Z, int S, int util_kind, const double* util_params, int n_util_params, const double* theta,
                               int theta_dim, const double* prob, int L, const double* best, double* acq_out, double* dacq_out, int* floored_out) {
   static const char* who = "bocf_acq_joint";
-  if (bocf_check_posterior(c, who)) return -1;
   const UtilArgs u{util_kind, util_params, n_util_params, theta, theta_dim, prob, L};
-  if (bocf_util_check_kind(who, u, "the joint acquisition does not take a utility program (BOCF_UTIL_PROGRAM): use one of the compiled-in utilities")) return -1;
-  int j0, mg, m;
-  if (bocf_group_range(c, who, -1, &j0, &mg, &m)) return -1;
-  if (m > BOCF_MAX_M) return fail(who, "more outputs per hyper-sample than the device utilities take (16)");
-  if (bocf_util_check(who, u, m, BOCF_EU_MC)) return -1;
-  if (q < 1 || q > JOINT_MAX_Q) return fail(who, "q out of range (1 .. 8)");
-  if (!Z) return fail(who, "null Z");
-  if (S < 1 || S > 256) return fail(who, "S out of range (1 .. 256)");
-  if (c->C < 1) return fail(who, "no resident candidates (bocf_set_candidates)");
-  if (c->C % q) return fail(who, "the number of resident candidates is not a multiple of q");
-  if (c->d > BOCF_MAX_D) return fail(who, "input dimension too large");
-  if (c->best_group >= c->m / m) return fail(who, "option best_group is not a valid hyper-sample index");
+  const int m = bocf_joint_check(who, bocf_call_state(c), u, q, Z, S);
+  if (m < 0) return -1;
   const int Ha = bocf_acq_hyper_count(c);
-  mg = Ha * m;
+  const int mg = Ha * m;
   const int C = c->C, d = c->d, N = c->N, Np = c->Np, B = C / q;
   const bool grad = dacq_out != nullptr;
   const double cap = (double)c->workspace_mb * 1048576.0;
@@ -54,7 +43,7 @@ extern "C" int bocf_acq_joint(bocf_ctx* c, int q, const double* Z, int S, int ut
       for (int i = 0; i < q; ++i) c->jt_tail[((size_t)j * q + i) * S + s] = Z[((size_t)s * m + j) * q + i];
   for (size_t i = 0; i < nbest; ++i) c->jt_tail[nZ + i] = best[i];
   const UtilPack& pk = bocf_util_pack(u, c->jt_tail.data(), c->jt_tail.size(), &c->util_up);
-  if (c->jt_par.ensure(pk.bytes()) || c->jt_best.ensure(sizeof(double) * (size_t)Ha * L) || c->jt_fl.ensure(sizeof(int) * (size_t)B) ||
+  if (c->jt_best.ensure(sizeof(double) * (size_t)Ha * L) || c->jt_fl.ensure(sizeof(int) * (size_t)B) ||
       c->jt_V.ensure(sizeof(double) * (size_t)mg * Np * cap_p) || c->jt_mu.ensure(sizeof(double) * (size_t)mg * cap_p) ||
       c->jt_cov.ensure(sizeof(double) * (size_t)mg * cap_p * cap_p) || c->acq.ensure(sizeof(double) * (size_t)round_up(C, BOCF_TILE)))
     return -1;
@@ -63,7 +52,7 @@ extern "C" int bocf_acq_joint(bocf_ctx* c, int q, const double* Z, int S, int ut
                c->jt_E.ensure(sizeof(double) * (size_t)C * m * S) || c->jt_dout.ensure(sizeof(double) * (size_t)C * d)))
     return -1;
   c->have_acq = false;
-  HIPCHK(hipMemcpyAsync(c->jt_par.p, pk.host.data(), pk.bytes(), hipMemcpyHostToDevice, c->stream));
+  if (bocf_upload_util(c, pk, &c->jt_par)) return -1;
   const double* par = c->jt_par.as<double>();
   JointArgs a{};
   a.theta = par + pk.theta; a.theta_dim = theta_dim; a.prob = par + pk.prob; a.L = L; a.util_params = par + pk.params; a.Zt = par + pk.tail;

@@ -13,14 +13,6 @@ void bocf_kg_drop(bocf_ctx* c) { c->kg_na = 0; }
 
 static KgRefSet kg_ref(bocf_ctx* c) { return KgRefSet{&c->kg_XA, &c->kg_VA, &c->kg_Wa, c->kg_na}; }
 
-static int kg_ready(bocf_ctx* c, const char* who) {
-  if (bocf_check_posterior(c, who)) return -1;
-  if (c->kg_na < 1) return fail(who, "no reference points: call bocf_set_ref_points after the fit");
-  if (c->C < 1) return fail(who, "no resident candidates (bocf_set_candidates)");
-  if (c->d > BOCF_MAX_D) return fail(who, "input dimension too large");
-  return 0;
-}
-
 static const char* kWorkspace = "the look-ahead workspace exceeds option workspace_mb: fewer candidates or a larger cap";
 
 // candidates per chunk: V of a chunk (mg x Np x chunk doubles) stays under the cap; 0 when not even 128 fit
@@ -104,7 +96,7 @@ int bocf_kg_chunk_dcov(bocf_ctx* c, const KgRefSet& ref, int j0, int mg, int c0,
 
 extern "C" int bocf_set_ref_points(bocf_ctx* c, const double* Xa, int na) {
   static const char* who = "bocf_set_ref_points";
-  if (bocf_check_posterior(c, who)) return -1;
+  if (bocf_check_posterior(who, bocf_call_state(c))) return -1;
   if (!Xa) return fail(who, "null Xa");
   if (na < 1 || na > KG_MAX_REF) return fail(who, "na out of range (1 .. 1024)");
   if (c->d > BOCF_MAX_D) return fail(who, "input dimension too large");
@@ -129,10 +121,10 @@ extern "C" int bocf_set_ref_points(bocf_ctx* c, const double* Xa, int na) {
 
 extern "C" int bocf_cov_to_ref(bocf_ctx* c, int group, double* cov_out, double* dcov_out) {
   static const char* who = "bocf_cov_to_ref";
-  if (kg_ready(c, who)) return -1;
+  if (bocf_kg_ready(who, bocf_call_state(c))) return -1;
   if (!cov_out) return fail(who, "null cov_out");
   int j0, mg, per;
-  if (bocf_group_range(c, who, group, &j0, &mg, &per)) return -1;
+  if (bocf_group_range(who, bocf_call_state(c), group, &j0, &mg, &per)) return -1;
   const int C = c->C, d = c->d, na = c->kg_na, nap = round_up(na, BOCF_TILE);
   const int chunk = bocf_kg_chunk_size(c, mg);
   if (chunk < BOCF_TILE) return fail(who, kWorkspace);
@@ -158,11 +150,11 @@ extern "C" int bocf_cov_to_ref(bocf_ctx* c, int group, double* cov_out, double* 
 
 extern "C" int bocf_conditioned_variance(bocf_ctx* c, int group, int q, double* var_out, double* dvar_out) {
   static const char* who = "bocf_conditioned_variance";
-  if (kg_ready(c, who)) return -1;
+  if (bocf_kg_ready(who, bocf_call_state(c))) return -1;
   if (!var_out) return fail(who, "null var_out");
   if (q < 0 || q >= c->kg_na) return fail(who, "q out of range (0 .. na - 1)");
   int j0, mg, per;
-  if (bocf_group_range(c, who, group, &j0, &mg, &per)) return -1;
+  if (bocf_group_range(who, bocf_call_state(c), group, &j0, &mg, &per)) return -1;
   const int C = c->C, d = c->d, nap = round_up(c->kg_na, BOCF_TILE);
   const int chunk = bocf_kg_chunk_size(c, mg);
   if (chunk < BOCF_TILE) return fail(who, kWorkspace);
@@ -191,21 +183,11 @@ extern "C" int bocf_conditioned_variance(bocf_ctx* c, int group, int q, double* 
 extern "C" int bocf_acq_kg(bocf_ctx* c, int mode, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim,
                            const double* prob, int L, const double* Zf, int Sf, double* acq_out, double* dacq_out) {
   static const char* who = "bocf_acq_kg";
-  if (bocf_check_posterior(c, who)) return -1;
-  if (mode < BOCF_EU_MEAN || mode > BOCF_EU_MC) return fail(who, "unknown mode");
   const UtilArgs u{util_kind, util_params, n_util_params, theta, theta_dim, prob, L};
-  if (bocf_util_check_kind(who, u, "the knowledge gradient does not take a utility program (BOCF_UTIL_PROGRAM): use one of the compiled-in utilities")) return -1;
-  int j0, mg, m;
-  if (bocf_group_range(c, who, -1, &j0, &mg, &m)) return -1;
-  if (m > BOCF_MAX_M) return fail(who, "more outputs per hyper-sample than the device utilities take (16)");
-  if (bocf_util_check(who, u, m, mode)) return -1;
-  if (!Zf) return fail(who, "null Zf");
-  if (Sf < 1 || Sf > 256) return fail(who, "Sf out of range (1 .. 256)");
-  if (mode == BOCF_EU_MC && c->S_mc < 1) return fail(who, "no Monte-Carlo samples set (bocf_set_mc_samples)");
-  if (mode == BOCF_EU_MC && c->S_mc > 256) return fail(who, "more than 256 Monte-Carlo samples");
-  if (kg_ready(c, who)) return -1;
+  const int m = bocf_kg_check(who, bocf_call_state(c), mode, u, Zf, Sf);
+  if (m < 0) return -1;
   const int Ha = bocf_acq_hyper_count(c);                   // the convention of the other acquisitions
-  mg = Ha * m;
+  const int mg = Ha * m;
   const int C = c->C, d = c->d, na = c->kg_na, nap = round_up(na, BOCF_TILE);
   const bool grad = dacq_out != nullptr;
   int chunk = bocf_kg_chunk_size(c, mg);
@@ -217,13 +199,12 @@ extern "C" int bocf_acq_kg(bocf_ctx* c, int mode, int util_kind, const double* u
   HIPCHK(hipSetDevice(c->device));
   // theta | prob | utility parameters | Zf in one upload
   const UtilPack& pk = bocf_util_pack(u, Zf, (size_t)Sf * m, &c->util_up);
-  if (c->kg_par.ensure(pk.bytes()) || c->kg_v0.ensure(sizeof(double) * (size_t)Ha * L) || c->acq.ensure(sizeof(double) * (size_t)round_up(C, BOCF_TILE)))
-    return -1;
+  if (c->kg_v0.ensure(sizeof(double) * (size_t)Ha * L) || c->acq.ensure(sizeof(double) * (size_t)round_up(C, BOCF_TILE))) return -1;
   if (grad && (c->kg_dout.ensure(sizeof(double) * (size_t)C * d) || c->kg_astar.ensure(sizeof(int) * (size_t)C * L * Sf) ||
                c->kg_AB.ensure(sizeof(double) * (size_t)C * L * Sf * 2 * m)))
     return -1;
   c->have_acq = false;
-  HIPCHK(hipMemcpyAsync(c->kg_par.p, pk.host.data(), pk.bytes(), hipMemcpyHostToDevice, c->stream));
+  if (bocf_upload_util(c, pk, &c->kg_par)) return -1;
   KgArgs a{};
   a.ldc = nap; a.lda = nap; a.nug = c->kg_nug.as<double>();
   a.theta = c->kg_par.as<double>() + pk.theta; a.theta_dim = theta_dim; a.prob = c->kg_par.as<double>() + pk.prob; a.L = L;

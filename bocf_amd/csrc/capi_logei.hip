@@ -10,12 +10,6 @@
 #include "logei.h"
 #include "logei_args.h"
 
-// what the checks of logei_args.h read from the context
-static LogEiState logei_state(const bocf_ctx* c) {
-  if (!c) return LogEiState{};
-  return LogEiState{c->fitted, c->canned, c->m, c->hyper_samples, c->best_group, c->S_mc, c->d, c->C};
-}
-
 // theta | prob | utility parameters in one upload, the posterior, the incumbents of every hyper-sample, one launch, the pair to the host
 static int logei_run(bocf_ctx* c, UtilArgs u, int m, bool closed, double tau, double* acq_out, double* dacq_out) {
   static const double no_theta[BOCF_MAX_L] = {0.0};         // a program without parameters: one unread column
@@ -24,8 +18,7 @@ static int logei_run(bocf_ctx* c, UtilArgs u, int m, bool closed, double tau, do
   if (u.theta_dim == 0) { u.theta = no_theta; u.theta_dim = 1; }
   HIPCHK(hipSetDevice(c->device));
   const UtilPack& pk = bocf_util_pack(u, nullptr, 0, &c->util_up);
-  if (c->lg_par.ensure(pk.bytes()) || c->lg_best.ensure(sizeof(double) * (size_t)Ha * u.L)) return -1;
-  HIPCHK(hipMemcpyAsync(c->lg_par.p, pk.host.data(), pk.bytes(), hipMemcpyHostToDevice, c->stream));
+  if (c->lg_best.ensure(sizeof(double) * (size_t)Ha * u.L) || bocf_upload_util(c, pk, &c->lg_par)) return -1;
   c->have_acq = false;
   if (bocf_acq_posterior(c, grad)) return -1;
   const double* par = c->lg_par.as<double>();
@@ -45,14 +38,12 @@ static int logei_run(bocf_ctx* c, UtilArgs u, int m, bool closed, double tau, do
   if (closed) launch_logei_linear(a, grad, c->stream);
   else launch_logei_mc(a, grad, c->stream);
   t.stop();
-  c->have_acq = true;
-  const size_t b0 = acq_out ? sizeof(double) * (size_t)c->C : 0, b1 = grad ? sizeof(double) * (size_t)c->C * c->d : 0;
-  return bocf_copy_pair_out(c, c->acq.p, acq_out, b0, c->dacq.p, dacq_out, b1);
+  return bocf_acq_finish(c, acq_out, dacq_out);
 }
 
 extern "C" int bocf_acq_log_linear(bocf_ctx* c, const double* theta, const double* prob, int L, double* acq_out, double* dacq_out) {
   static const char* who = "bocf_acq_log_linear";
-  const int m = bocf_log_linear_check(who, logei_state(c), theta, L, dacq_out != nullptr);
+  const int m = bocf_log_linear_check(who, bocf_call_state(c), theta, L, dacq_out != nullptr);
   if (m < 0) return -1;
   return logei_run(c, UtilArgs{BOCF_UTIL_LINEAR, nullptr, 0, theta, m, prob, L}, m, true, 1.0, acq_out, dacq_out);   // theta is (L, m)
 }
@@ -62,7 +53,7 @@ extern "C" int bocf_acq_log_mc(bocf_ctx* c, double tau, int util_kind, const dou
   static const char* who = "bocf_acq_log_mc";
   const UtilArgs u{util_kind, util_params, n_util_params, theta, theta_dim, prob, L};
   bool program;
-  const int m = bocf_log_mc_check(who, logei_state(c), tau, u, dacq_out != nullptr, &program);
+  const int m = bocf_log_mc_check(who, bocf_call_state(c), tau, u, dacq_out != nullptr, &program);
   if (m < 0) return -1;
   if (program && bocf_check_resident_program(c, who, m, theta_dim, n_util_params)) return -1;
   return logei_run(c, u, m, false, tau, acq_out, dacq_out);

@@ -26,7 +26,7 @@ static int loo_enqueue(bocf_ctx* c, const char* who, int flags, int j0, int mg) 
 
 extern "C" int bocf_loo(bocf_ctx* c, int flags, double* mean_out, double* var_out, double* lpd_out, double* lpd_sum_out) {
   static const char* who = "bocf_loo";
-  if (bocf_check_posterior(c, who)) return -1;
+  if (bocf_check_posterior(who, bocf_call_state(c))) return -1;
   if (flags & ~(BOCF_ADD_NOISE | BOCF_CLIP)) return fail(who, "unknown flags (BOCF_ADD_NOISE | BOCF_CLIP)");
   HIPCHK(hipSetDevice(c->device));
   const int N = c->N, Np = c->Np, m = c->m;
@@ -47,37 +47,18 @@ extern "C" int bocf_loo(bocf_ctx* c, int flags, double* mean_out, double* var_ou
 extern "C" int bocf_loo_utility(bocf_ctx* c, int group, int flags, int mode, int util_kind, const double* util_params, int n_util_params,
                                 const double* theta, int theta_dim, int L, double* val_out) {
   static const char* who = "bocf_loo_utility";
-  if (bocf_check_posterior(c, who)) return -1;
-  if (flags & ~(BOCF_ADD_NOISE | BOCF_CLIP)) return fail(who, "unknown flags (BOCF_ADD_NOISE | BOCF_CLIP)");
-  if (mode < BOCF_EU_MEAN || mode > BOCF_EU_MC) return fail(who, "unknown mode");
-  if (group < 0) return fail(who, "group out of range (0 .. hyper_samples - 1)");
-  int j0, mg, m;
-  if (bocf_group_range(c, who, group, &j0, &mg, &m)) return -1;
-  if (m > BOCF_MAX_M) return fail(who, "more outputs per hyper-sample than the device utilities take (16)");
+  const CallState st = bocf_call_state(c);
   const UtilArgs u{util_kind, util_params, n_util_params, theta, theta_dim, nullptr, L};
-  if (util_kind == BOCF_UTIL_PROGRAM && mode != BOCF_EU_MEAN) {
-    if (mode == BOCF_EU_CLOSED) return fail(who, "a utility program has no closed-form expectation (BOCF_EU_CLOSED): use the Monte-Carlo mode");
-    if (L < 1 || L > BOCF_MAX_L) return fail(who, "L out of range (1 .. 32)");
-    if (theta_dim < 1 || theta_dim > BOCF_MAX_M || !theta) return fail(who, "theta must be (L, 1 <= theta_dim <= 16)");
-    if (bocf_check_resident_program(c, who, m, theta_dim, n_util_params)) return -1;
-  } else {
-    if (util_kind < BOCF_UTIL_LINEAR || util_kind > BOCF_UTIL_PROGRAM) return fail(who, "unknown utility kind");
-    UtilArgs k = u;
-    if (mode == BOCF_EU_MEAN) k.kind = BOCF_UTIL_LINEAR;     // (the mean form ignores the kind)
-    if (bocf_util_check(who, k, m, mode)) return -1;
-  }
-  if (mode == BOCF_EU_MC) {
-    if (c->eu_S < 1) return fail(who, "no Monte-Carlo samples set (bocf_set_eu_samples)");
-    if (c->eu_L < L) return fail(who, "fewer Monte-Carlo sample blocks than parameters (bocf_set_eu_samples)");
-    if (c->eu_m != m) return fail(who, "the Monte-Carlo samples were set for another output count (bocf_set_eu_samples)");
-  }
-  if (!val_out) return fail(who, "null val_out");
+  bool program;
+  const int m = bocf_loo_utility_check(who, st, group, flags, mode, u, &program);
+  if (m < 0 || (program && bocf_check_resident_program(c, who, m, theta_dim, n_util_params))) return -1;
+  if (bocf_loo_utility_check_call(who, st, mode, L, m, val_out)) return -1;
   HIPCHK(hipSetDevice(c->device));
-  const int N = c->N, Np = c->Np;
+  const int N = c->N, Np = c->Np, j0 = group * m;            // hyper-sample `group` is outputs [j0, j0 + m)
   const UtilPack& pk = bocf_util_pack(u, nullptr, 0, &c->util_up);
-  if (c->loo_par.ensure(pk.bytes()) || c->loo_rows.ensure(sizeof(int) * (size_t)L * N) || c->loo_val.ensure(sizeof(double) * (size_t)L * N)) return -1;
-  if (loo_enqueue(c, who, flags, j0, mg)) return -1;
-  HIPCHK(hipMemcpyAsync(c->loo_par.p, pk.host.data(), pk.bytes(), hipMemcpyHostToDevice, c->stream));
+  if (c->loo_rows.ensure(sizeof(int) * (size_t)L * N) || c->loo_val.ensure(sizeof(double) * (size_t)L * N)) return -1;
+  if (loo_enqueue(c, who, flags, j0, m)) return -1;
+  if (bocf_upload_util(c, pk, &c->loo_par)) return -1;
   launch_loo_rows(c->loo_rows.as<int>(), N, L, c->stream);
   const size_t plane = (size_t)c->m * Np;
   EuArgs a{};

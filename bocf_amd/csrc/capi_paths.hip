@@ -32,9 +32,9 @@ struct PathBlock {
 
 extern "C" int bocf_set_paths(bocf_ctx* c, int group, const double* omega, const double* phase, const double* weights, const double* eps, int F, int S) {
   static const char* who = "bocf_set_paths";
-  if (bocf_check_posterior(c, who)) return -1;
+  if (bocf_check_posterior(who, bocf_call_state(c))) return -1;
   int j0, mg, per;
-  if (bocf_group_range(c, who, group, &j0, &mg, &per)) return -1;
+  if (bocf_group_range(who, bocf_call_state(c), group, &j0, &mg, &per)) return -1;
   const int H = c->m / per, h0 = group < 0 ? 0 : group, h1 = group < 0 ? H : group + 1;
   if (S == 0) {                                              // drop the group's paths
     if ((int)c->pt_S.size() == H)
@@ -120,9 +120,9 @@ extern "C" int bocf_set_paths(bocf_ctx* c, int group, const double* omega, const
 
 extern "C" int bocf_path_values(bocf_ctx* c, int group, double* values_out) {
   static const char* who = "bocf_path_values";
-  if (bocf_check_posterior(c, who)) return -1;
+  if (bocf_check_posterior(who, bocf_call_state(c))) return -1;
   int j0, mg, per;
-  if (bocf_group_range(c, who, group, &j0, &mg, &per)) return -1;
+  if (bocf_group_range(who, bocf_call_state(c), group, &j0, &mg, &per)) return -1;
   const int H = c->m / per, h0 = group < 0 ? 0 : group, h1 = group < 0 ? H : group + 1;
   if ((int)c->pt_S.size() != H) return fail(who, kNoPaths);
   for (int h = h0; h < h1; ++h)
@@ -173,9 +173,9 @@ extern "C" int bocf_path_values(bocf_ctx* c, int group, double* values_out) {
 extern "C" int bocf_path_utility(bocf_ctx* c, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim, int P,
                                  const int* row_path, double* val_out, double* grad_out) {
   static const char* who = "bocf_path_utility";
-  if (bocf_check_posterior(c, who)) return -1;
+  if (bocf_check_posterior(who, bocf_call_state(c))) return -1;
   int j0, mg, per;
-  if (bocf_group_range(c, who, -1, &j0, &mg, &per)) return -1;
+  if (bocf_group_range(who, bocf_call_state(c), -1, &j0, &mg, &per)) return -1;
   const int H = c->m / per;
   int Pres = 0;
   if ((int)c->pt_S.size() == H)
@@ -189,7 +189,7 @@ extern "C" int bocf_path_utility(bocf_ctx* c, int util_kind, const double* util_
     if (row_path[r] < 0 || row_path[r] >= P) return fail(who, "row_path out of range (0 .. P - 1)");
   if (util_kind < BOCF_UTIL_LINEAR || util_kind > BOCF_UTIL_PROGRAM) return fail(who, "unknown utility kind");
   if (n_util_params < 0 || n_util_params > BOCF_MAX_M || (n_util_params > 0 && !util_params)) return fail(who, "too many utility parameters / null");
-  if (per > BOCF_MAX_M) return fail(who, "more outputs per hyper-sample than the device utilities take (16)");
+  if (bocf_check_group_fits(who, per)) return -1;
   if (util_kind == BOCF_UTIL_PROGRAM && bocf_check_resident_program(c, who, per, theta_dim, n_util_params)) return -1;
   HIPCHK(hipSetDevice(c->device));
   std::vector<double> par;                                   // the widened theta rows | the parameters (util_args.h)

@@ -16,7 +16,7 @@ static const char* kWorkspace = "the look-ahead workspace exceeds option workspa
 
 extern "C" int bocf_set_pending_points(bocf_ctx* c, const double* Xp, int r, const double* Zp, int S, int max_jitter_tries, double* jitter_out) {
   static const char* who = "bocf_set_pending_points";
-  if (bocf_check_posterior(c, who)) return -1;
+  if (bocf_check_posterior(who, bocf_call_state(c))) return -1;
   if (!Xp) return fail(who, "null Xp");
   if (r < 1 || r > PENDING_MAX_R) return fail(who, "r out of range (1 .. 15)");
   if (!Zp) return fail(who, "null Zp");
@@ -25,8 +25,7 @@ extern "C" int bocf_set_pending_points(bocf_ctx* c, const double* Xp, int r, con
   if (S != c->S_mc) return fail(who, "S must equal the number of resident Monte-Carlo samples (bocf_set_mc_samples)");
   if (c->d > BOCF_MAX_D) return fail(who, "input dimension too large");
   int j0, M, m;
-  if (bocf_group_range(c, who, -1, &j0, &M, &m)) return -1;
-  if (m > BOCF_MAX_M) return fail(who, "more outputs per hyper-sample than the device utilities take (16)");
+  if (bocf_group_range(who, bocf_call_state(c), -1, &j0, &M, &m) || bocf_check_group_fits(who, m)) return -1;
   const int Np = c->Np, d = c->d, rp = BOCF_TILE;
   if (2.0 * M * (double)Np * rp * sizeof(double) > (double)c->workspace_mb * 1048576.0) return fail(who, kWorkspace);
   HIPCHK(hipSetDevice(c->device));
@@ -66,7 +65,7 @@ extern "C" int bocf_set_pending_points(bocf_ctx* c, const double* Xp, int r, con
 
 extern "C" int bocf_get_pending_samples(bocf_ctx* c, double* F_out) {
   static const char* who = "bocf_get_pending_samples";
-  if (bocf_check_posterior(c, who)) return -1;
+  if (bocf_check_posterior(who, bocf_call_state(c))) return -1;
   if (c->pd_r < 1) return fail(who, "no pending points: call bocf_set_pending_points after the fit");
   if (!F_out) return fail(who, "null F_out");
   const size_t nQ = (size_t)c->m * c->pd_r * c->pd_r, nF = (size_t)c->m * c->pd_r * c->pd_S;
@@ -77,23 +76,11 @@ extern "C" int bocf_get_pending_samples(bocf_ctx* c, double* F_out) {
 extern "C" int bocf_acq_pending(bocf_ctx* c, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim,
                                 const double* prob, int L, double* acq_out, double* dacq_out) {
   static const char* who = "bocf_acq_pending";
-  if (bocf_check_posterior(c, who)) return -1;
   const UtilArgs u{util_kind, util_params, n_util_params, theta, theta_dim, prob, L};
-  if (bocf_util_check_kind(who, u, "the pending-point acquisition does not take a utility program (BOCF_UTIL_PROGRAM): use one of the compiled-in utilities"))
-    return -1;
-  int j0, mg, m;
-  if (bocf_group_range(c, who, -1, &j0, &mg, &m)) return -1;
-  if (m > BOCF_MAX_M) return fail(who, "more outputs per hyper-sample than the device utilities take (16)");
-  if (bocf_util_check(who, u, m, BOCF_EU_MC)) return -1;
-  if (c->S_mc < 1) return fail(who, "no Monte-Carlo samples set (bocf_set_mc_samples)");
-  if (c->S_mc > 256) return fail(who, "more than 256 Monte-Carlo samples");
-  if (c->pd_r < 1) return fail(who, "no pending points: call bocf_set_pending_points after the fit");
-  if (c->pd_S != c->S_mc) return fail(who, "the number of Monte-Carlo samples changed since bocf_set_pending_points");
-  if (c->C < 1) return fail(who, "no resident candidates (bocf_set_candidates)");
-  if (c->d > BOCF_MAX_D) return fail(who, "input dimension too large");
-  if (c->best_group >= c->m / m) return fail(who, "option best_group is not a valid hyper-sample index");
+  const int m = bocf_pending_check(who, bocf_call_state(c), u);
+  if (m < 0) return -1;
   const int Ha = bocf_acq_hyper_count(c);
-  mg = Ha * m;
+  const int mg = Ha * m;
   const int C = c->C, d = c->d, N = c->N, r = c->pd_r, S = c->pd_S, rp = BOCF_TILE;
   const bool grad = dacq_out != nullptr;
   const int chunk = bocf_kg_chunk_size(c, mg);
@@ -106,12 +93,12 @@ extern "C" int bocf_acq_pending(bocf_ctx* c, int util_kind, const double* util_p
   // theta | prob | utility parameters in one upload
   const UtilPack& pk = bocf_util_pack(u, nullptr, 0, &c->util_up);
   const int cap = round_up(C < chunk ? C : chunk, BOCF_TILE);
-  if (c->pd_par.ensure(pk.bytes()) || c->pd_best.ensure(sizeof(double) * (size_t)Ha * L) || c->pd_T.ensure(sizeof(double) * (size_t)Ha * L * S) ||
+  if (c->pd_best.ensure(sizeof(double) * (size_t)Ha * L) || c->pd_T.ensure(sizeof(double) * (size_t)Ha * L * S) ||
       c->pd_muc.ensure(sizeof(double) * (size_t)mg * cap) || c->acq.ensure(sizeof(double) * (size_t)round_up(C, BOCF_TILE)))
     return -1;
   if (grad && (c->kg_dout.ensure(sizeof(double) * (size_t)C * d) || c->pd_E.ensure(sizeof(double) * (size_t)C * m * S))) return -1;
   c->have_acq = false;
-  HIPCHK(hipMemcpyAsync(c->pd_par.p, pk.host.data(), pk.bytes(), hipMemcpyHostToDevice, c->stream));
+  if (bocf_upload_util(c, pk, &c->pd_par)) return -1;
   const size_t nQ = (size_t)c->m * r * r, nF = (size_t)c->m * r * S;
   const double* Qd = c->pd_QFG.as<double>();
   PendArgs a{};

@@ -1,7 +1,7 @@
 // bocf_refine_acq (include/bocf_hip.h): the acquisition optimiser's anchor refinement with the loop on the device.  What
 // bocf_lbfgsb_batched does between two callbacks -- each a candidate upload, an acquisition pass, a copy back and a synchronisation -- is one
 // more launch on the stream here (refine_advance_kernel, refine.hip): a pass is the posterior with its gradients and the acquisition of the
-// resident rows, exactly as bocf_acq_linear_grad / bocf_acq_mc_grad enqueue them (bocf_acq_grad_enqueue, capi.hip), then the step, which
+// resident rows, exactly as bocf_acq_linear_grad / bocf_acq_mc_grad enqueue them (bocf_acq_enqueue, capi.hip), then the step, which
 // writes every row's next trial point into the resident candidate rows.  The host only enqueues, and every poll_every passes reads ONE word.
 #include "bocf_ctx.h"
 #include "refine_step.h"
@@ -31,14 +31,16 @@ extern "C" int bocf_refine_acq(bocf_ctx* c, int form, int kind, int util_kind, c
   if (linear) {
     if (kind != BOCF_ACQ_EI && kind != BOCF_ACQ_PI) return fail(me, "unknown acquisition kind");
     if (!theta) return fail(me, "theta is null");
-    per = bocf_acq_group_size(c, me);
+    per = bocf_check_groups(me, bocf_call_state(c), true, true);
     if (per < 0) return -1;
     util_kind = BOCF_UTIL_LINEAR; util_params = nullptr; n_util_params = 0; theta_dim = per;
   } else {
-    per = bocf_acq_mc_group_size(c, me, util_kind, util_params, n_util_params, theta_dim);   // (a resident program is accepted: checked here)
-    if (per < 0) return -1;
+    bool program;                                            // (a resident program is accepted: checked here)
+    per = bocf_mc_utility_check(me, bocf_call_state(c), UtilArgs{util_kind, util_params, n_util_params, theta, theta_dim, prob, L}, &program);
+    if (per < 0 || (program && bocf_check_resident_program(c, me, per, theta_dim, n_util_params))) return -1;
     if (theta_dim > 0 && !theta) return fail(me, "theta is null");
     if (n_util_params < 0 || n_util_params > BOCF_MAX_M) return fail(me, "bad utility parameters");
+    kind = BOCF_ACQ_EI;                                      // (the Monte-Carlo gradient form has no other)
   }
   HIPCHK(hipSetDevice(c->device));
   RefineSettings s;
@@ -82,7 +84,7 @@ extern "C" int bocf_refine_acq(bocf_ctx* c, int form, int kind, int util_kind, c
   while (rc == 0 && passes < budget) {
     const long long n = budget - passes < poll_every ? budget - passes : poll_every;
     for (long long i = 0; i < n && rc == 0; ++i) {
-      if (!few) rc = bocf_acq_grad_enqueue(c, per, linear, kind, util_kind, n_util_params, theta_dim, L);
+      if (!few) rc = bocf_acq_enqueue(c, per, linear, true, kind, util_kind, n_util_params, theta_dim, L);
       // (the buffers are read after the enqueue: the first pass may have grown them)
       if (rc == 0 && !two) launch_refine_advance(c->acq.as<double>(), c->dacq.as<double>(), c->Xc.as<double>(), dbl, ints, running, A, s, lo, hi, c->stream);
       if (rc || !two) continue;
@@ -98,7 +100,7 @@ extern "C" int bocf_refine_acq(bocf_ctx* c, int form, int kind, int util_kind, c
       // later change keys to the candidate batch must be dropped here as bocf_set_candidates drops it)
       std::swap(c->Xc, c->rf_x2);
       c->C = BOCF_SMALL_N;
-      rc = bocf_acq_grad_enqueue(c, per, linear, kind, util_kind, n_util_params, theta_dim, L);
+      rc = bocf_acq_enqueue(c, per, linear, true, kind, util_kind, n_util_params, theta_dim, L);
       std::swap(c->Xc, c->rf_x2);
       c->C = A;
       if (rc == 0)

@@ -8,20 +8,13 @@
 #include "bocf_ctx.h"
 #include "risk_args.h"
 
-// what the checks of risk_args.h read from the context
-static RiskState risk_state(const bocf_ctx* c) {
-  if (!c) return RiskState{};
-  return RiskState{c->fitted, c->canned, c->m, c->hyper_samples, c->S_mc, c->d, c->C};
-}
-
 // theta | prob | utility parameters in one upload, the posterior, one launch per hyper-sample, the pair to the host
 static int risk_run(bocf_ctx* c, const UtilArgs& u, int m, RiskArgs a, bool closed, double* acq_out, double* dacq_out) {
   const bool grad = dacq_out != nullptr;
   const int Ha = bocf_acq_hyper_count(c);
   HIPCHK(hipSetDevice(c->device));
   const UtilPack& pk = bocf_util_pack(u, nullptr, 0, &c->util_up);
-  if (c->rk_par.ensure(pk.bytes())) return -1;
-  HIPCHK(hipMemcpyAsync(c->rk_par.p, pk.host.data(), pk.bytes(), hipMemcpyHostToDevice, c->stream));
+  if (bocf_upload_util(c, pk, &c->rk_par)) return -1;
   c->have_acq = false;
   if (bocf_acq_posterior(c, grad)) return -1;
   const double* par = c->rk_par.as<double>();
@@ -32,26 +25,19 @@ static int risk_run(bocf_ctx* c, const UtilArgs& u, int m, RiskArgs a, bool clos
   // the hyper-sample loop of bocf_acq_mc: hyper-sample h reads rows [h m, (h + 1) m) of the posterior and adds its share
   for (int h = 0; h < Ha; ++h) {
     PhaseTimer t(c, "acq");
-    a.mean = c->mean.as<double>() + (size_t)h * m * a.ld;
-    a.var = c->var.as<double>() + (size_t)h * m * a.ld;
-    if (grad) {
-      a.dmean = c->dmean.as<double>() + (size_t)h * m * a.ldg * a.d;
-      a.dvar = c->dvar.as<double>() + (size_t)h * m * a.ldg * a.d;
-    }
+    bocf_posterior_rows(c, h, m, grad, &a);
     a.accumulate = h > 0;
     if (closed) launch_linear_ucb(a, grad, c->stream);
     else launch_risk(a, grad, c->stream);
   }
-  c->have_acq = true;
-  const size_t b0 = acq_out ? sizeof(double) * (size_t)c->C : 0, b1 = grad ? sizeof(double) * (size_t)c->C * c->d : 0;
-  return bocf_copy_pair_out(c, c->acq.p, acq_out, b0, c->dacq.p, dacq_out, b1);
+  return bocf_acq_finish(c, acq_out, dacq_out);
 }
 
 extern "C" int bocf_acq_risk(bocf_ctx* c, int kind, int rank, int util_kind, const double* util_params, int n_util_params, const double* theta,
                              int theta_dim, const double* prob, int L, double* acq_out, double* dacq_out) {
   static const char* who = "bocf_acq_risk";
   const UtilArgs u{util_kind, util_params, n_util_params, theta, theta_dim, prob, L};
-  const int m = bocf_risk_check(who, risk_state(c), kind, rank, u, dacq_out != nullptr);
+  const int m = bocf_risk_check(who, bocf_call_state(c), kind, rank, u, dacq_out != nullptr);
   if (m < 0) return -1;
   RiskArgs a{};
   a.kind = kind; a.rank = rank; a.S = c->S_mc; a.Wt = c->Wt.as<double>();
@@ -60,7 +46,7 @@ extern "C" int bocf_acq_risk(bocf_ctx* c, int kind, int rank, int util_kind, con
 
 extern "C" int bocf_acq_linear_ucb(bocf_ctx* c, double kappa, const double* theta, const double* prob, int L, double* acq_out, double* dacq_out) {
   static const char* who = "bocf_acq_linear_ucb";
-  const int m = bocf_ucb_check(who, risk_state(c), kappa, theta, prob, L, dacq_out != nullptr);
+  const int m = bocf_ucb_check(who, bocf_call_state(c), kappa, theta, prob, L, dacq_out != nullptr);
   if (m < 0) return -1;
   const UtilArgs u{BOCF_UTIL_LINEAR, nullptr, 0, theta, m, prob, L};           // theta is (L, m)
   RiskArgs a{};

@@ -10,28 +10,6 @@ void bocf_thompson_drop(bocf_ctx* c) {
   for (int& s : c->ts_S) s = 0;
 }
 
-// the outputs `group` selects: hyper-sample h's [h m', (h + 1) m') (m' = outputs per hyper-sample), or all of them for -1
-int bocf_group_range(bocf_ctx* c, const char* who, int group, int* j0, int* mg, int* per) {
-  const int H = c->hyper_samples > 0 ? c->hyper_samples : 1;
-  if (c->m % H) return fail(who, "the fitted outputs are not a whole number of hyper-samples (option hyper_samples)");
-  *per = c->m / H;
-  if (group == -1) {
-    *j0 = 0;
-    *mg = c->m;
-    return 0;
-  }
-  if (group < 0 || group >= H) return fail(who, "group out of range (-1 or 0 .. hyper_samples - 1)");
-  *j0 = group * *per;
-  *mg = *per;
-  return 0;
-}
-
-int bocf_check_posterior(bocf_ctx* c, const char* who) {
-  if (!c || !c->fitted) return fail(who, "model not fitted");
-  if (c->canned) return fail(who, "the context holds a host-given posterior (bocf_set_posterior): it has no factor to sample from; fit first");
-  return 0;
-}
-
 static int check_workspace(bocf_ctx* c, const char* who, int mg, long rows, long cols) {
   const double bytes = (double)mg * (double)rows * (double)cols * sizeof(double);
   if (bytes > (double)c->workspace_mb * 1048576.0) return fail(who, "the covariance matrices exceed option workspace_mb: fewer candidates or a larger cap");
@@ -61,11 +39,11 @@ int bocf_enqueue_V(bocf_ctx* c, int j0, int mg, const double* Xq, int n, int npa
 
 extern "C" int bocf_posterior_cov(bocf_ctx* c, const double* X1, int n1, const double* X2, int n2, int group, double* cov_out) {
   static const char* who = "bocf_posterior_cov";
-  if (bocf_check_posterior(c, who)) return -1;
+  if (bocf_check_posterior(who, bocf_call_state(c))) return -1;
   if (!X1 || !X2 || !cov_out) return fail(who, "null argument");
   if (n1 < 1 || n2 < 1) return fail(who, "n1 and n2 must be >= 1");
   int j0, mg, per;
-  if (bocf_group_range(c, who, group, &j0, &mg, &per)) return -1;
+  if (bocf_group_range(who, bocf_call_state(c), group, &j0, &mg, &per)) return -1;
   const int d = c->d, Np = c->Np;
   const int n1p = round_up(n1, BOCF_TILE), n2p = round_up(n2, BOCF_TILE);
   if (check_workspace(c, who, mg, n1p, n2p)) return -1;
@@ -117,13 +95,13 @@ struct BorrowStream {
 
 extern "C" int bocf_posterior_samples(bocf_ctx* c, int group, const double* Z, int S, int max_jitter_tries, double* samples_out, double* jitter_out) {
   static const char* who = "bocf_posterior_samples";
-  if (bocf_check_posterior(c, who)) return -1;
+  if (bocf_check_posterior(who, bocf_call_state(c))) return -1;
   if (!Z) return fail(who, "null Z");
   if (S < 1 || S > 256) return fail(who, "S out of range (1 .. 256)");
   const int C = c->C;
   if (C < 1) return fail(who, "no resident candidates (bocf_set_candidates)");
   int j0, mg, per;
-  if (bocf_group_range(c, who, group, &j0, &mg, &per)) return -1;
+  if (bocf_group_range(who, bocf_call_state(c), group, &j0, &mg, &per)) return -1;
   const int H = c->m / per, h0 = group < 0 ? 0 : group, h1 = group < 0 ? H : group + 1;
   const int d = c->d, Np = c->Np, Cp = round_up(C, BOCF_TILE), nbc = Cp / BOCF_TILE;
   const long strideS = (long)Cp * Cp;
@@ -229,7 +207,7 @@ extern "C" int bocf_posterior_samples(bocf_ctx* c, int group, const double* Z, i
 extern "C" int bocf_thompson_select(bocf_ctx* c, int util_kind, const double* util_params, int n_util_params, const double* theta, int theta_dim, int k,
                                     long long* idx_out, double* val_out) {
   static const char* who = "bocf_thompson_select";
-  if (bocf_check_posterior(c, who)) return -1;
+  if (bocf_check_posterior(who, bocf_call_state(c))) return -1;
   int P = 0;
   for (int s : c->ts_S) P += s;
   if (P == 0) return fail(who, "no resident samples: call bocf_posterior_samples first");
@@ -238,7 +216,7 @@ extern "C" int bocf_thompson_select(bocf_ctx* c, int util_kind, const double* ut
   if (!idx_out || (theta_dim > 0 && !theta) || theta_dim < 0) return fail(who, "null argument / bad theta_dim");
   if (util_kind < BOCF_UTIL_LINEAR || util_kind > BOCF_UTIL_PROGRAM) return fail(who, "unknown utility kind");
   if (n_util_params < 0 || n_util_params > BOCF_MAX_M || (n_util_params > 0 && !util_params)) return fail(who, "too many utility parameters / null");
-  if (per > BOCF_MAX_M) return fail(who, "more outputs per hyper-sample than the device utilities take (16)");
+  if (bocf_check_group_fits(who, per)) return -1;
   if (util_kind == BOCF_UTIL_PROGRAM && bocf_check_resident_program(c, who, per, theta_dim, n_util_params)) return -1;
   HIPCHK(hipSetDevice(c->device));
   std::vector<double> par;                                   // the widened theta rows | the parameters (util_args.h)

@@ -31,7 +31,7 @@ int main() {
     char* bar3 = bar2 ? strchr(bar2 + 1, '|') : nullptr;
     if (!bar3) return fprintf(stderr, "bad line: %s", line), 2;
     *bar1 = *bar2 = *bar3 = 0;
-    CeuState s{};
+    CallState s{};
     int need_constraints, kind, n_params, params_null, theta_null, theta_dim, L, u0_mode, rows_mode, n_hyps, val_null, grad;
     if (sscanf(bar1 + 1, "%d %d %d %d %d %d %d %d %d %d %d %d %d", &s.fitted, &s.canned, &s.m, &s.hyper_samples, &s.best_group, &s.cq_K, &s.cq_m, &s.eu_S,
                &s.eu_L, &s.eu_m, &s.d, &s.C, &need_constraints) != 13)
@@ -50,7 +50,7 @@ int main() {
     if (rows_mode == 3 && !rows.empty()) rows.back() = -1;
     double val = 0.0;
     g_failed = 0;
-    const int m = bocf_ceu_check_utility(line, s, u, need_constraints != 0);
+    const int m = bocf_constrained_utility(line, s, u, need_constraints != 0, BOCF_CEU_NO_PROGRAM);
     int rc = m < 0 ? -1 : 0;
     if (rc == 0 && need_constraints)
       rc = bocf_ceu_check_call(line, s, u, m, u0_mode && !u0.empty() ? u0.data() : nullptr, rows_mode && !rows.empty() ? rows.data() : nullptr, n_hyps,

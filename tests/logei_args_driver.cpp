@@ -25,7 +25,7 @@ int main() {
     char* bar3 = bar2 ? strchr(bar2 + 1, '|') : nullptr;
     if (!bar3) return fprintf(stderr, "bad line: %s", line), 2;
     *bar1 = *bar2 = *bar3 = 0;
-    LogEiState s{};
+    CallState s{};
     int kind, n_params, params_null, theta_null, theta_dim, L, grad;
     char tau_text[64];
     if (sscanf(bar1 + 1, "%d %d %d %d %d %d %d %d", &s.fitted, &s.canned, &s.m, &s.hyper_samples, &s.best_group, &s.S_mc, &s.d, &s.C) != 8)
